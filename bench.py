@@ -7,8 +7,14 @@ table in HBM; with N > 1 also the RCCL all-to-all exchange and the final
 per-owner reduce.  The corpus is generated on the host (synthetic, seeded) and
 copied to HBM before timing.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds what takes runs of its own: the CPU baseline, the sorted-result steps and
+the per-phase diagnostic step at N = 1, the hash-order steps and the same-work
+N = 1 figure at N > 1.  --dump-outputs DIR writes the table of the last timed
+step (what a caller of the timed path fetches) as DIR/<name>.npy.
 
 With --gpus N > 1 and no torchrun environment, ONE process drives all N GPUs
 through an engine group (mox_config.n_gpus, include/mox.h): a step is one
@@ -67,13 +73,18 @@ def parse():
     # profiles/r05/bench_warmup_transient.txt); 20 untimed passes measure the
     # steady state (C2: warmup 3 -> 927-931 GB/s, 10 -> 965-969, 20 -> 974-976)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: CPU baseline, sorted-result steps and per-phase "
+                         "diagnostic step (N = 1); hash-order steps and same-work N = 1 figure (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the table of the last timed step as DIR/<name>.npy (float64 / float32, <= 64 MB)")
     ap.add_argument("--workload", default="", choices=[""] + sorted(WORKLOADS),
                     help="default: C2 at N = 1, C3 (8 GiB shard per GPU) at N > 1")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the final tables on their owner ranks")
     ap.add_argument("--cpu-runs", type=int, default=3, help="CPU baseline: median of this many runs")
     ap.add_argument("--bytes-per-gpu", type=int, default=0, help="override the shard size")
     ap.add_argument("--cpu-sample-mib", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-dict", action="store_true")
     ap.add_argument("--sample-pieces", type=int, default=0, help="dictionary sample pieces (0 = engine default)")
     ap.add_argument("--sync-passes", action="store_true", help="N = 1: synchronous passes (no async enqueue)")
@@ -84,12 +95,52 @@ def parse():
                     help="diagnostics: no HIP events around k_map in the timed steps (no roofline.achieved)")
     ap.add_argument("--traffic-json", default=None,  # profiles/pmc_k_map.json (C2) or pmc_k_map_<workload>.json
                     help="PMC summary of the map kernel (tools/pmc_traffic.py) to report as roofline.traffic")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def progress(msg):
     """A progress line on stderr (long runs keep writing, so a watchdog sees them alive)."""
     print("[bench %s] %s" % (time.strftime("%H:%M:%S"), msg), file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET = 64 * 10**6  # bytes of .npy payload per --dump-outputs directory
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(dirpath, counts, offs, raw, tokens):
+    """The fetched table of the last timed step as .npy files: counts[i] and
+    word_bytes[word_offsets[i]:word_offsets[i+1]] are word i in table order,
+    tokens the table's token total.  A table past DUMP_BUDGET is cut to a
+    fixed, seeded sample of its words (sample_index = their table positions)."""
+    os.makedirs(dirpath, exist_ok=True)
+    counts = np.asarray(counts, dtype=np.uint64)
+    offs = np.asarray(offs, dtype=np.int64)
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    n = counts.size
+    out = {"tokens": np.array([tokens], dtype=np.float64), "n_words": np.array([n], dtype=np.float64)}
+    cost = lambda k, nb: 24 * k + 8 + 4 * nb  # noqa: E731  (counts, offsets, index in f64; bytes in f32)
+    if n and cost(n, buf.size) > DUMP_BUDGET - 4096:
+        lens = np.diff(offs)
+        k = n
+        while True:
+            k = max(1, int(k * min(0.9, (DUMP_BUDGET - 4096) / cost(k, buf.size * k / n))))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+            klen = lens[idx]
+            if cost(k, int(klen.sum())) <= DUMP_BUDGET - 4096 or k == 1:
+                break
+        koffs = np.zeros(k + 1, np.int64)
+        np.cumsum(klen, out=koffs[1:])
+        pos = np.repeat(offs[idx], klen) + (np.arange(int(koffs[-1])) - np.repeat(koffs[:-1], klen))
+        counts, offs, buf = counts[idx], koffs, buf[pos]
+        out["sample_index"] = idx.astype(np.float64)
+    out["counts"] = counts.astype(np.float64)
+    out["word_offsets"] = offs.astype(np.float64)
+    out["word_bytes"] = buf.astype(np.float32)
+    for name, arr in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
 
 
 def cpu_model():
@@ -264,21 +315,28 @@ def main_group(a):
         g.synchronize()  # member 0's stream drained: the last step's sort / gather tail is inside the clock
         return time.perf_counter() - t0, rows
 
-    progress("shards in HBM; hash-order steps")
-    el_hash, rows_hash = timed(base_flags)
+    el_hash, rows_hash = None, None
+    if a.full:
+        progress("shards in HBM; hash-order steps")
+        el_hash, rows_hash = timed(base_flags)
     progress("sorted-result steps")
     elapsed, rows = timed(base_flags | mox.MOX_F_SORT_BYTES)  # the value: sorted result inside the step
     last = rows[-1]
-    progress("same-work N = 1 steps (member 0's shard alone)")
-    e1 = mox.Engine(device=devices[0] if devices else 0, flags=base_flags | mox.MOX_F_TIMING_MAP | mox.MOX_F_SORT_BYTES,
-                    sample_pieces=a.sample_pieces, reserve_bytes=per_rank)
-    n1 = same_work_n1(e1, shards[0], per_rank, a.steps, a.warmup, n, total / (elapsed / a.steps) / 1e9)
-    e1.close()
     t = g.fetch()  # bytewise order (sorted on GPU 0 by the last timed step)
     counts, offs, raw = t.arrays()
     table_n, table_bytes, table_tokens = t.n, int(offs[-1]) if t.n else 0, t.tokens
     ok = int(counts.sum()) == t.tokens == last["tokens"]
     t.close()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, counts, offs, raw, table_tokens)
+    del counts, offs, raw
+    n1 = None
+    if a.full:
+        progress("same-work N = 1 steps (member 0's shard alone)")
+        e1 = mox.Engine(device=devices[0] if devices else 0, flags=base_flags | mox.MOX_F_TIMING_MAP | mox.MOX_F_SORT_BYTES,
+                        sample_pieces=a.sample_pieces, reserve_bytes=per_rank)
+        n1 = same_work_n1(e1, shards[0], per_rank, a.steps, a.warmup, n, total / (elapsed / a.steps) / 1e9)
+        e1.close()
     ms_step = elapsed / a.steps * 1e3
     gbs = total / (elapsed / a.steps) / 1e9
     map_avg = statistics.mean(r["ms_map"] for r in rows)
@@ -317,7 +375,8 @@ def main_group(a):
         "hash_order": {"value": round(total / (el_hash / a.steps) / 1e9, 3), "ms_per_step": round(el_hash / a.steps * 1e3, 4),
                        "note": "the same steps without the bytewise sort (gathered table in engine order)",
                        "phases_ms": {"local_passes": mean(rows_hash, "ms_local"), "exchange": mean(rows_hash, "ms_exchange"),
-                                     "gather": mean(rows_hash, "ms_gather"), "step_wall": mean(rows_hash, "ms_run")}},
+                                     "gather": mean(rows_hash, "ms_gather"), "step_wall": mean(rows_hash, "ms_run")}}
+                      if a.full else None,
         "stats": {k: last[k] for k in ("tokens", "uniques", "cold_records", "weighted_records")},
         "multi_gpu": {
             "mode": "engine group (one process)",
@@ -441,9 +500,19 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    sort_ms = eng.stats()["ms_sort"] if gather else 0.0  # this rank's sort of its byte range (sorted exchange)
+    last = eng.stats()
+    sort_ms = last["ms_sort"] if gather else 0.0  # this rank's sort of its byte range (sorted exchange)
+    # the table of the last timed step, as a caller of the timed path fetches it
+    t = eng.fetch()
+    counts, offs, raw = t.arrays()
+    ok = int(counts.sum()) == t.tokens
+    table_n, table_bytes, table_tokens = t.n, int(offs[-1]) if t.n else 0, t.tokens
+    t.close()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, counts, offs, raw, table_tokens)
+    del counts, offs, raw
     el_hash = None
-    if world > 1 and gather:  # the same steps without the sort, reported beside the value
+    if a.full and world > 1 and gather:  # the same steps without the sort, reported beside the value
         eng.set_flags(base_flags | mox.MOX_F_TIMING_MAP)  # hash-owned exchange, gathered table in engine order
         if dist:
             dist.barrier()
@@ -455,7 +524,7 @@ def main():
             dist.barrier()
         el_hash = time.perf_counter() - t1
     n1 = None
-    if world > 1 and gather:
+    if a.full and world > 1 and gather:
         # the same-work N = 1 figure: rank 0 alone on its shard while the others wait
         if dist:
             dist.barrier()
@@ -467,7 +536,7 @@ def main():
         if dist:
             dist.barrier()
     sorted_result = None
-    if world == 1:
+    if a.full and world == 1:
         # like-for-like with the N > 1 line (whose step ends in the bytewise
         # sort of the gathered table): the same K steps, each a synchronous pass
         # followed by the device bytewise sort of its table (mox_sort_result)
@@ -490,22 +559,19 @@ def main():
         except mox.MoxError as ex:  # e.g. a table past the device sort's 4 GiB of word bytes (C4)
             eng.synchronize()
             sorted_result = {"value": None, "note": "device bytewise sort not available for this table: %s" % ex}
-    eng.set_flags(base_flags | mox.MOX_F_TIMING)  # untimed diagnostic step: per-phase events
-    step(sync=True)
-    eng.synchronize()
-    phases = [eng.stats()]
+    phases = None
+    if a.full:
+        eng.set_flags(base_flags | mox.MOX_F_TIMING)  # untimed diagnostic step: per-phase events
+        step(sync=True)
+        eng.synchronize()
+        phases = [eng.stats()]
+        last = phases[0]
     if dist:
         import torch
         t = torch.tensor([elapsed, el_hash or 0.0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0].item())
         el_hash = float(t[1].item()) if el_hash is not None else None
-    last = eng.stats()
-    t = eng.fetch()
-    counts, offs, _ = t.arrays()
-    ok = int(counts.sum()) == t.tokens
-    table_n, table_bytes, table_tokens = t.n, int(offs[-1]) if t.n else 0, t.tokens
-    t.close()
     xinfo = None
     if dist:
         import torch
@@ -581,7 +647,7 @@ def main():
             "pass_mode": "async (mox_run_range_async: back-to-back passes, each completed and checked)" if use_async else "sync",
             "phases_ms": {k: round(statistics.mean(p[k] for p in phases), 4)
                           for k in ("ms_run", "ms_dict", "ms_map", "ms_lanes", "ms_reduce", "ms_finalize",
-                                    "ms_exchange", "ms_gather")},
+                                    "ms_exchange", "ms_gather")} if phases else None,
             "stats": {k: last[k] for k in ("tokens", "uniques", "dict_words", "cold_records", "weighted_records",
                                            "unicode_tokens", "long_tokens", "chunks", "max_subpasses", "retries",
                                            "reduce_units", "split_partitions")},
@@ -591,7 +657,7 @@ def main():
             "check_sum_counts_eq_tokens": ok,
             "cpu_baseline": None,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(kind, seed, min(per_rank, a.cpu_sample_mib << 20), a.cpu_runs)
         print(json.dumps(line), flush=True)
     eng.free(d_buf)

@@ -356,7 +356,7 @@ def test_bench_eight_members_without_torchrun():
     multi_gpu fields, so that the driver's 8-GPU run can only fail in RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--xport", "host", "--device", "0",
-           "--steps", "2", "--warmup", "1", "--bytes-per-gpu", str(128 << 20), "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--bytes-per-gpu", str(128 << 20), "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -374,7 +374,7 @@ def test_bench_torchrun_processes_host_transport():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--xport", "host", "--device", "0", "--steps", "2", "--warmup", "1",
-           "--bytes-per-gpu", str(64 << 20)]
+           "--bytes-per-gpu", str(64 << 20), "--full"]
     r = subprocess.run(cmd, capture_output=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])

@@ -5,7 +5,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 VARS=$1; ROUNDS=${2:-2}; shift 2
-ARGS=${@:---steps 20 --warmup 5 --no-cpu-baseline}
+ARGS=${@:---steps 20 --warmup 5 --full --no-cpu-baseline}
 O=gpurun_out/ab; mkdir -p $O
 for v in $VARS; do
   MOX_LIB=build/var_$v/libmox.so timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 200 \

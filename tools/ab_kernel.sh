@@ -11,7 +11,7 @@ for v in $VARS; do
   for d in $DBGS; do
     D=$O/${v}_$d
     MOX_LIB=build/var_$v/libmox.so MOX_DBG=$d timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $D -o run -- \
-      python3 bench.py $ARGS > $D.log 2>&1
+      python3 bench.py --full $ARGS > $D.log 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "$v dbg $d rc=$rc"; tail -3 $D.log; exit $rc; }
     python3 - "$D/run_kernel_stats.csv" "$v dbg=$d" "$D.log" $KS <<'PY'
 import csv, json, sys

@@ -8,7 +8,7 @@ TAG=${1:-stages}; STAGES=${2:-4096 1 2 0}; VAR=${VAR:-abl}; KRE=${KRE:-k_map}; U
 O=gpurun_out/$TAG; mkdir -p $O
 for d in $STAGES; do
   MOX_LIB=build/var_$VAR/libmox.so MOX_DBG=$d timeout -s KILL 90 rocprofv3 --pmc SQ_INSTS_VALU,SQ_INSTS_SALU,SQ_INSTS_LDS,SQ_INSTS_BRANCH,SQ_ACTIVE_INST_VALU,SQ_WAVE_CYCLES,SQ_WAIT_ANY,SQ_INSTS_SMEM \
-    --kernel-include-regex "$KRE" --output-format csv -d $O/d$d -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --sync-passes > $O/d$d.log 2>&1
+    --kernel-include-regex "$KRE" --output-format csv -d $O/d$d -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sync-passes > $O/d$d.log 2>&1
   rc=$?; [ $rc -eq 0 ] || { echo "dbg $d rc=$rc"; tail -3 $O/d$d.log; exit $rc; }
   python3 - $O/d$d $d $UNITS <<'PY'
 import csv, glob, sys, collections

@@ -9,7 +9,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 for vd in $RUNS; do
   v=${vd%%:*}; d=${vd##*:}
   MOX_LIB=build/var_$v/libmox.so MOX_DBG=$d timeout -s KILL 90 rocprofv3 --pmc TCP_UTCL1_TRANSLATION_MISS_sum,TCP_UTCL1_TRANSLATION_HIT_sum,TCP_TCC_READ_REQ_LATENCY_sum,TCP_TCC_READ_REQ_sum \
-    --kernel-include-regex "$KRE" --output-format csv -d $O/${v}_$d -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --sync-passes > $O/${v}_$d.log 2>&1
+    --kernel-include-regex "$KRE" --output-format csv -d $O/${v}_$d -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sync-passes > $O/${v}_$d.log 2>&1
   rc=$?; [ $rc -eq 0 ] || { echo "$vd rc=$rc"; tail -n 3 $O/${v}_$d.log; exit $rc; }
   python3 - $O/${v}_$d $vd <<'PY'
 import csv, glob, sys, collections

@@ -49,10 +49,10 @@ fast_suite() {
 case $SEC in
 evid)
   fast_suite
-  timeout -k 10 400 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
+  timeout -k 10 400 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
   cut -c1-200 $O/bench_c2.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2 -o run -- \
-    python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/c2_under_rocprof.log 2>&1; step "rocprof C2" $?
+    python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/c2_under_rocprof.log 2>&1; step "rocprof C2" $?
   python3 tools/trace_timeline.py $O/c2 > $O/c2_timeline.txt; step "timeline C2" $?
   tail -1 $O/c2_timeline.txt
   ;;
@@ -63,10 +63,10 @@ slow)
   rc=$?; tail -15 $O/gpu_slow.log; step slow $rc
   ;;
 n2)
-  timeout -k 10 400 python -u bench.py --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2.json 2> $O/n2.err; step "bench n2" $?
+  timeout -k 10 400 python -u bench.py --full --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2.json 2> $O/n2.err; step "bench n2" $?
   python3 -c "import json;d=json.load(open('$O/n2.json'));print(d['value'],d['phases_ms'],d.get('hash_order'))"
   timeout -k 10 500 rocprofv3 --kernel-trace --memory-copy-trace --hip-runtime-trace --output-format csv -d $O/n2t -o run -- \
-    python3 bench.py --gpus 2 --xport host --device 0 --steps 2 --warmup 1 > $O/n2t.json 2> $O/n2t.err; step "rocprof n2" $?
+    python3 bench.py --full --gpus 2 --xport host --device 0 --steps 2 --warmup 1 > $O/n2t.json 2> $O/n2t.err; step "rocprof n2" $?
   python3 tools/step_timeline.py $O/n2t 100 > $O/n2_timeline.txt; step "timeline" $?
   tail -3 $O/n2_timeline.txt
   ;;
@@ -82,7 +82,7 @@ redabl)
   bash tools/ab_kernel.sh "abl" "0 64 128 512 32" "k_reduce" > $O/red_abl.txt 2>&1; rc=$?; cat $O/red_abl.txt; step redabl $rc
   for d in 1024 1088; do
     mkdir -p $O/s$d
-    MOX_LIB=build/var_abl/libmox.so MOX_DBG=$d MOX_DEBUG_DIR=$O/s$d timeout -k 10 200 python -u bench.py --steps 3 --warmup 1 \
+    MOX_LIB=build/var_abl/libmox.so MOX_DBG=$d MOX_DEBUG_DIR=$O/s$d timeout -k 10 200 python -u bench.py --full --steps 3 --warmup 1 \
       --no-cpu-baseline > $O/s$d.log 2>&1; step "stamps $d" $?
     echo "dbg $d"; python3 tools/stamps.py $O/s$d/stamps.csv
   done
@@ -98,11 +98,11 @@ pmc)
 lines)
   # C4 / C5 bench lines (production build) and a C4 kernel trace + timeline
   for wl in C4 C5; do
-    timeout -k 10 500 python -u bench.py --workload $wl --steps 5 --warmup 2 > $O/bench_$wl.json 2> $O/bench_$wl.err; step "bench $wl" $?
+    timeout -k 10 500 python -u bench.py --full --workload $wl --steps 5 --warmup 2 > $O/bench_$wl.json 2> $O/bench_$wl.err; step "bench $wl" $?
     python3 -c "import json;d=json.loads(open('$O/bench_$wl.json').read().strip().splitlines()[-1]);print('$wl',d['value'],d['ms_per_step'],d['phases_ms'])"
   done
   timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4 -o run -- \
-    python3 bench.py --workload C4 --steps 3 --warmup 1 --no-cpu-baseline > $O/c4_under_rocprof.log 2>&1; step "rocprof C4" $?
+    python3 bench.py --full --workload C4 --steps 3 --warmup 1 --no-cpu-baseline > $O/c4_under_rocprof.log 2>&1; step "rocprof C4" $?
   python3 tools/trace_timeline.py $O/c4 > $O/c4_timeline.txt; step "timeline C4" $?
   tail -1 $O/c4_timeline.txt
   ;;

@@ -33,10 +33,10 @@ newtests)
   pyt async_c2.log 400 tests/test_gpu_scale.py -m gpu -k "async_bench_mode"
   ;;
 evid)
-  timeout -k 10 400 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
+  timeout -k 10 400 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
   cut -c1-300 $O/bench_c2.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2 -o run -- \
-    python3 bench.py --no-cpu-baseline > $O/c2_under_rocprof.log 2>&1; step "rocprof C2" $?
+    python3 bench.py --full --no-cpu-baseline > $O/c2_under_rocprof.log 2>&1; step "rocprof C2" $?
   python3 tools/trace_timeline.py $O/c2 > $O/c2_timeline.txt; step "timeline C2" $?
   tail -1 $O/c2_timeline.txt
   ;;
@@ -61,7 +61,7 @@ mapdiag)
   # (-DMOX_ABLATE builds, MOX_DBG=4096: rows released untouched)
   for v in ${DIAG_STAMP:-ringst selfst}; do
     mkdir -p $O/$v
-    MOX_LIB=build/var_$v/libmox.so MOX_DBG=1024 MOX_DEBUG_DIR=$O/$v timeout -k 10 200 python -u bench.py --steps 3 --warmup 1 \
+    MOX_LIB=build/var_$v/libmox.so MOX_DBG=1024 MOX_DEBUG_DIR=$O/$v timeout -k 10 200 python -u bench.py --full --steps 3 --warmup 1 \
       --no-cpu-baseline > $O/$v.log 2>&1; step "stamps $v" $?
     echo "$v"; python3 tools/mapcyc.py $O/$v/mapcyc.csv
   done
@@ -72,7 +72,7 @@ xsort)
   # and the N = 2 engine-group bench line (2 x 8 GiB C3 shards on GPU 0)
   pyt xsort_tests.log 900 tests/test_gpu_exchange.py tests/test_gpu_group.py -m "gpu and not slow"
   pyt xsort_c3.log 900 tests/test_gpu_scale.py -m gpu -k "c3_group"
-  timeout -k 10 400 python -u bench.py --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2.json 2> $O/n2.err; step "bench n2" $?
+  timeout -k 10 400 python -u bench.py --full --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2.json 2> $O/n2.err; step "bench n2" $?
   python3 -c "import json;d=json.load(open('$O/n2.json'));print(d['value'],d['phases_ms'],d.get('hash_order'))"
   ;;
 varc2)
@@ -86,11 +86,11 @@ stages)
 lines)
   # bench lines of the other configs: C5, C4 (16 GiB each), and the N = 2
   # engine group (2 x 8 GiB C3 shards on GPU 0, device-copy transport, sorted result)
-  timeout -k 10 420 python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --workload C5 > $O/bench_c5.json 2> $O/bench_c5.err; step "bench C5" $?
+  timeout -k 10 420 python -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --workload C5 > $O/bench_c5.json 2> $O/bench_c5.err; step "bench C5" $?
   cut -c1-200 $O/bench_c5.json
-  timeout -k 10 600 python -u bench.py --steps 3 --warmup 2 --no-cpu-baseline --workload C4 > $O/bench_c4.json 2> $O/bench_c4.err; step "bench C4" $?
+  timeout -k 10 600 python -u bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --workload C4 > $O/bench_c4.json 2> $O/bench_c4.err; step "bench C4" $?
   cut -c1-200 $O/bench_c4.json
-  timeout -k 10 500 python -u bench.py --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/bench_n2.json 2> $O/bench_n2.err; step "bench N2 group" $?
+  timeout -k 10 500 python -u bench.py --full --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/bench_n2.json 2> $O/bench_n2.err; step "bench N2 group" $?
   cut -c1-200 $O/bench_n2.json
   ;;
 pmc)

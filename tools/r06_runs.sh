@@ -55,19 +55,19 @@ smoke)
   step "smoke $(tail -1 $O/smoke.log)" $?
   ;;
 evid)
-  timeout -k 10 400 python -u bench.py > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
+  timeout -k 10 400 python -u bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
   cut -c1-300 $O/bench_c2.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2 -o run -- \
-    python3 bench.py --no-cpu-baseline > $O/c2_under_rocprof.log 2>&1; step "rocprof C2" $?
+    python3 bench.py --full --no-cpu-baseline > $O/c2_under_rocprof.log 2>&1; step "rocprof C2" $?
   python3 tools/trace_timeline.py $O/c2 > $O/c2_timeline.txt; step "timeline C2" $?
   tail -1 $O/c2_timeline.txt
   ;;
 n2)
-  timeout -k 10 500 python -u bench.py --gpus 2 --xport host --device 0 --steps 5 --warmup 2 > $O/bench_n2.json 2> $O/bench_n2.err
+  timeout -k 10 500 python -u bench.py --full --gpus 2 --xport host --device 0 --steps 5 --warmup 2 > $O/bench_n2.json 2> $O/bench_n2.err
   step "bench N2 group" $?
   cut -c1-300 $O/bench_n2.json
   timeout -k 10 500 rocprofv3 --kernel-trace --hip-trace --memory-copy-trace --output-format csv -d $O/n2tr -o run -- \
-    python3 bench.py --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2_under_rocprof.log 2>&1; step "rocprof N2" $?
+    python3 bench.py --full --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2_under_rocprof.log 2>&1; step "rocprof N2" $?
   python3 tools/step_timeline.py $O/n2tr 30 > $O/n2_step_timeline.txt; step "step timeline N2" $?
   tail -3 $O/n2_step_timeline.txt
   ;;
@@ -76,7 +76,7 @@ abn2)
   k=0
   for v in $AB_VARS; do
     k=$((k+1)); f=$O/abn2_${k}_${v}
-    MOX_LIB=build/var_$v/libmox.so timeout -k 10 400 python -u bench.py --gpus 2 --xport host --device 0 --steps 5 --warmup 2 > $f.json 2> $f.err
+    MOX_LIB=build/var_$v/libmox.so timeout -k 10 400 python -u bench.py --full --gpus 2 --xport host --device 0 --steps 5 --warmup 2 > $f.json 2> $f.err
     rc=$?; [ $rc -eq 0 ] || { tail -3 $f.err; step "abn2 $v" $rc; }
     python3 -c "import json;d=json.loads(open('$f.json').read().strip().splitlines()[-1]);m=d['multi_gpu'];h=d['hash_order'];print('$v', d['value'], 'exchange', m['exchange_ms'], 'sort', d['phases_ms']['sort_bytes'], 'hash', h['value'], h['phases_ms']['exchange'])"
   done
@@ -85,7 +85,7 @@ n2prof)
   # kernel trace of an N = 2 group bench (VAR=name: build/var_name), the exchange reduce passes' kernels
   L=${VAR:+build/var_$VAR/libmox.so}; L=${L:-map-oxidize_amd/mox/libmox.so}
   MOX_LIB=$L timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/n2k_${VAR:-tree} -o run -- \
-    python3 bench.py --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2k_${VAR:-tree}.log 2>&1; step "rocprof N2 ${VAR:-tree}" $?
+    python3 bench.py --full --gpus 2 --xport host --device 0 --steps 3 --warmup 1 > $O/n2k_${VAR:-tree}.log 2>&1; step "rocprof N2 ${VAR:-tree}" $?
   python3 tools/xpass_kernels.py $O/n2k_${VAR:-tree} > $O/xpass_${VAR:-tree}.txt; step "xpass ${VAR:-tree}" $?
   cat $O/xpass_${VAR:-tree}.txt
   ;;
@@ -94,15 +94,15 @@ abs)
   k=0
   for v in $AB_VARS; do
     k=$((k+1)); f=$O/abs_${k}_${v}
-    MOX_LIB=build/var_$v/libmox.so timeout -k 10 300 python -u bench.py --no-cpu-baseline ${AB_ARGS:-} > $f.json 2> $f.err
+    MOX_LIB=build/var_$v/libmox.so timeout -k 10 300 python -u bench.py --full --no-cpu-baseline ${AB_ARGS:-} > $f.json 2> $f.err
     rc=$?; [ $rc -eq 0 ] || { tail -3 $f.err; step "abs $v" $rc; }
     python3 -c "import json;d=json.loads(open('$f.json').read().strip().splitlines()[-1]);s=d['sorted_result'];print('$v', d['value'], 'sorted', s['value'], 'sort_ms', s.get('sort_bytes_ms'))"
   done
   ;;
 lines)
-  timeout -k 10 420 python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --workload C5 > $O/bench_c5.json 2> $O/bench_c5.err; step "bench C5" $?
+  timeout -k 10 420 python -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --workload C5 > $O/bench_c5.json 2> $O/bench_c5.err; step "bench C5" $?
   cut -c1-200 $O/bench_c5.json
-  timeout -k 10 600 python -u bench.py --steps 3 --warmup 2 --no-cpu-baseline --workload C4 > $O/bench_c4.json 2> $O/bench_c4.err; step "bench C4" $?
+  timeout -k 10 600 python -u bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --workload C4 > $O/bench_c4.json 2> $O/bench_c4.err; step "bench C4" $?
   cut -c1-200 $O/bench_c4.json
   ;;
 ab)
@@ -114,7 +114,7 @@ abe)
   for spec in $AB_VARS; do
     k=$((k+1)); v=${spec%@*}; sp=""; [ "$spec" != "$v" ] && sp="--sample-pieces ${spec#*@}"
     f=$O/abe_${k}_${v}
-    MOX_LIB=build/var_$v/libmox.so timeout -k 10 300 python -u bench.py --no-cpu-baseline $sp ${AB_ARGS:-} > $f.json 2> $f.err
+    MOX_LIB=build/var_$v/libmox.so timeout -k 10 300 python -u bench.py --full --no-cpu-baseline $sp ${AB_ARGS:-} > $f.json 2> $f.err
     rc=$?; [ $rc -eq 0 ] || { tail -3 $f.err; step "abe $spec" $rc; }
     python3 -c "import json,sys;d=json.loads(open('$f.json').read().strip().splitlines()[-1]);print('$spec', d['value'], d['roofline']['avg_launch_ms'], d['stats']['cold_records'], d['stats']['dict_words'])"
   done
@@ -133,7 +133,7 @@ evab)
   for k in 1 2; do
     for v in ev noev; do
       f=$O/evab_${k}_$v.json; x=""; [ $v = noev ] && x="--no-map-events"
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline $x > $f 2> $O/evab_${k}_$v.err; step "evab $k $v" $?
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline $x > $f 2> $O/evab_${k}_$v.err; step "evab $k $v" $?
       python3 -c "import json;d=json.loads(open('$f').read().strip().splitlines()[-1]);print('$v', d['value'], d['ms_per_step'])"
     done
   done
@@ -143,13 +143,13 @@ overlap)
   cat $O/overlap.txt
   ;;
 c2)
-  timeout -k 10 400 python -u bench.py --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
+  timeout -k 10 400 python -u bench.py --full --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err; step "bench C2" $?
   python3 -c "import json;d=json.loads(open('$O/bench_c2.json').read().strip().splitlines()[-1]);print(d['value'], d['roofline']['avg_launch_ms'], d['sorted_result'])"
   ;;
 c2prof)
   # rocprofv3 kernel stats of the C2 bench (no CPU baseline): the sort kernels' averages
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c2p -o run -- \
-    python3 bench.py --no-cpu-baseline > $O/c2p_under_rocprof.log 2>&1; step "rocprof C2" $?
+    python3 bench.py --full --no-cpu-baseline > $O/c2p_under_rocprof.log 2>&1; step "rocprof C2" $?
   f=$(ls $O/c2p/*/run_kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] || f=$(ls $O/c2p/run_kernel_stats.csv)
   cut -d, -f1-4 "$f" | grep -E "k_ss_|k_os_pass|k_bs_|k_scan|k_map|k_reduce\"" ; true
   python3 tools/sort_timeline.py $O/c2p > $O/sort_timeline.txt; step "sort timeline" $?
