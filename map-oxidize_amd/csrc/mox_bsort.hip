@@ -753,7 +753,14 @@ int bsort_once(mox_engine* e, bool checked) {
   const uint64_t ntiles = (n + OS_TILE - 1) / OS_TILE;
   // scratch: records A, B, subset S, payload | run flags, positions | status | gh, gs | scan sums | totals, err
   // (a table whose per-digit status regions would pass 256 MiB reuses one region)
-  const bool one_region = 8ull * OS_DIGITS * 256 * ntiles > (256ull << 20);
+  bool one_region = 8ull * OS_DIGITS * 256 * ntiles > (256ull << 20);
+  // MOX_BSORT_ONE_REGION=1 (tests): the single reused region at any table size
+  if (const char* v = getenv("MOX_BSORT_ONE_REGION"))
+    if (strtoull(v, nullptr, 10)) one_region = true;
+  // MOX_BSORT_TMP_MAX=<bytes> (tests): a first scratch request above it counts
+  // as failed, so the record arrays borrow the pass buffers as on a full GPU
+  uint64_t tmp_max = ~0ull;
+  if (const char* v = getenv("MOX_BSORT_TMP_MAX")) tmp_max = strtoull(v, nullptr, 10);
   // (every array a multiple of 256 bytes: what follows stays aligned for its 8-byte atomics)
   const uint64_t rec = (16 * n + 255) & ~255ull, u64n = (8 * n + 255) & ~255ull, u32n = (4 * n + 255) & ~255ull;
   const uint64_t sums = 8ull * scan_sum_words(n);
@@ -769,7 +776,7 @@ int bsort_once(mox_engine* e, bool checked) {
     return rc;
   uint64_t need = small;
   for (uint64_t b : big) need += b;
-  rc = grow_dev(e->s_tmp, need);
+  rc = need > tmp_max ? (int)MOX_ENOMEM : grow_dev(e->s_tmp, need);
   if (rc == MOX_ENOMEM) {
     (void)hipGetLastError();  // the failed hipMalloc's error is not a later launch's
     const Work& w = e->w;  // (the table is in t_*, or in the gather / sort buffers: never in these)
@@ -808,8 +815,12 @@ int bsort_once(mox_engine* e, bool checked) {
   if (rc) return rc;
   if (!e->h_bsort) HIPCHK(hipHostMalloc((void**)&e->h_bsort, OS_DIGITS * 256 * 8 + 64, hipHostMallocDefault));
   uint8_t* q = (uint8_t*)e->s_tmp.p;
-  for (int k = 0; k < 6; k++)
+  int n_big = 0, n_borrowed = 0;  // the big arrays in use, and those that live in borrowed pass buffers
+  for (int k = 0; k < 6; k++) {
+    n_big += big[k] != 0;
+    n_borrowed += bp[k] != nullptr;
     if (!bp[k] && big[k]) { bp[k] = q; q += big[k]; }
+  }
   BRec* A = (BRec*)bp[0];
   BRec* B = (BRec*)bp[1];
   BRec* S = (BRec*)bp[2];  // (nullptr unless checked: then the free ping-pong buffer below)
@@ -827,6 +838,21 @@ int bsort_once(mox_engine* e, bool checked) {
   uint64_t* total = (uint64_t*)q; q += 64;  // [0] subset size [1] runs
   s.err = (unsigned int*)q;
   uint64_t* h_tot = (uint64_t*)(e->h_bsort + OS_DIGITS * 256);
+  // the carve-up keeps every array aligned for its widest access (16-byte
+  // record loads, 8-byte atomics and status words), also with borrowed arrays
+  {
+    const struct { const char* name; const void* p; uintptr_t align; } arr[] = {
+        {"A", A, 16}, {"B", B, 16}, {"S", S, 16}, {"pay", pay, 16}, {"fin", fin, 8}, {"lrun", lrun, 8},
+        {"tick", s.tick, 8}, {"status", s.status, 8}, {"gh", s.gh, 8}, {"gs", s.gs, 8}, {"ssum", ssum, 8},
+        {"total", total, 8}, {"pos", pos, 4}, {"err", s.err, 4}};
+    for (const auto& a : arr)
+      if ((uintptr_t)a.p % a.align)
+        return fail(MOX_EHIP, "bytewise sort: scratch array %s at %p is not %d-byte aligned (%llu words)", a.name, a.p,
+                    (int)a.align, (unsigned long long)n);
+  }
+  if (e->verbose)
+    fprintf(stderr, "bsort: n=%llu checked=%d one_region=%d borrowed=%d/%d\n", (unsigned long long)n, checked ? 1 : 0,
+            one_region ? 1 : 0, n_borrowed, n_big);
   // err: [0] look-back timeout [1] radix fallback [2] long runs (k_bs_segsort); gh; total / rbs; tickets + status
   {
     const uint64_t nst = (TICK_BYTES + (one_region ? 1 : 8) * (uint64_t)ntiles * 256 * 8) / 8;  // level 0: 8 digits
