@@ -188,7 +188,12 @@ int mox_run_device(mox_engine* e, const void* d_text, size_t len);
  * give the left context (own_begin == 0 means "corpus start"); bytes after
  * own_end are look-ahead for the last token.  at_corpus_end != 0 means the
  * buffer end is the end of the corpus; otherwise a token reaching the buffer
- * end is an error (MOX_EHALO). */
+ * end is an error (MOX_EHALO).  A token reaches the end when no whole
+ * whitespace character follows it inside the buffer: one ending exactly at the
+ * end, or followed by a whitespace character that the end cuts, counts.  A
+ * character whose first byte lies in [own_begin, own_end) and that the end of
+ * a non-final buffer cuts is MOX_EHALO as well, whether or not its token is
+ * owned (at the corpus end it is MOX_EUTF8). */
 int mox_run_range(mox_engine* e, const void* d_buf, size_t buf_len, size_t own_begin, size_t own_end,
                   int at_corpus_end);
 /* Asynchronous mox_run_range: enqueues the pass and returns; the pass queued

@@ -46,6 +46,10 @@ class Utf8Error(MoxError):
     """Input is not valid UTF-8 (reference: tokio lines() -> InvalidData)."""
 
 
+class HaloError(MoxError):
+    """MOX_EHALO: an owned token or character runs past the end of a non-final shard buffer."""
+
+
 MAX_GPUS = 16
 XPORT_RCCL = 0  # engine group: RCCL communicators over xGMI
 XPORT_COPY = 1  # engine group: device-to-device copies (members may share a GPU)
@@ -202,6 +206,8 @@ def _check(rc, L=None):
         msg = (L or lib()).mox_last_error().decode("utf-8", "replace")
         if rc == MOX_EUTF8:
             raise Utf8Error(rc, msg)
+        if rc == MOX_EHALO:
+            raise HaloError(rc, msg)
         raise MoxError(rc, msg)
 
 

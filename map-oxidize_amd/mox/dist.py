@@ -6,8 +6,11 @@ merge of per-rank tables.  The gather itself is device side (mox_gather).
 The reference runs one process (main.rs:16-22); sharding is this engine's
 addition.  Every token belongs to the rank whose byte range holds its first
 byte; a rank's buffer carries 64 bytes of left context and HALO bytes of
-look-ahead so it can finish its last token (the engine reports MOX_EHALO if a
-token runs past the look-ahead).
+look-ahead so it can finish its last token (the engine reports MOX_EHALO,
+mox.HaloError, if a token runs past the look-ahead: it ends at or after the
+buffer end, or the whitespace character after it is cut there).  A character
+whose first byte is owned and that the end of a non-final buffer cuts is
+MOX_EHALO too, even inside a token of the rank before.
 """
 import heapq
 

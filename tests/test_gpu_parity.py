@@ -101,14 +101,17 @@ def test_fuzz_small(eng):
 
 
 def test_tile_boundaries(eng):
-    """Tokens, multi-byte whitespace and UTF-8 sequences straddling 16 B lanes and 16 KiB tiles."""
+    """Tokens, multi-byte whitespace and UTF-8 sequences straddling 16 B lanes,
+    the 992-byte rows of k_map and 16 KiB (the tiles of an earlier kernel; row
+    edges item by item: test_gpu_window.py)."""
     rng = random.Random(77)
     tile = 16 * 1024
+    row = 992  # mox_internal.h PAY
     for _ in range(40):
         n = rng.randint(tile - 64, 3 * tile + 64)
         buf = bytearray(rng.choice(b"abcdefghABCDEF  \n") for _ in range(n))
         for _ in range(30):  # plant tricky items at lane / tile edges
-            edge = rng.choice([tile, 2 * tile, 16 * rng.randint(1, n // 16 - 1)]) + rng.randint(-3, 2)
+            edge = rng.choice([tile, 2 * tile, row * rng.randint(1, n // row - 1), 16 * rng.randint(1, n // 16 - 1)]) + rng.randint(-3, 2)
             item = rng.choice([b"W" * rng.randint(15, 40), "　".encode(), " ".encode(),
                                "ΣΣ".encode(), "xİy".encode(), b"\x00\x00", b"Q" * 16, b"q" * 17])
             if 0 <= edge and edge + len(item) <= n:
