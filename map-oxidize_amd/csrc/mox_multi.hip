@@ -1029,6 +1029,9 @@ int reduce_received(mox_engine* e, uint64_t rs, uint64_t rb, uint64_t r_long, co
   for (int attempt = 0;; attempt++) {
     if ((rc = exchange_pass_once(e, rs, rb, rdir))) return rc;
     const Ctl& h = *e->h_ctl;
+    if (e->verbose)  // the unit summary of run_corpus's attempt line, for the reduce-only pass
+      fprintf(stderr, "[mox] reduce-only attempt %d: overflow 0x%x w_total %llu n_total %llu; units %llu, sort2 list %llu, k_reduce list %llu, k_reduce_small list %llu, split partitions %u, max sub-passes %u\n",
+              attempt, h.overflow, h.w_total, h.n_total, h.n_units, h.n_mid, h.n_big, h.n_small, h.n_split, h.max_sub);
     if ((rc = check_failed(h))) return rc;
     if (!h.overflow) break;
     if (h.overflow & OVF_REDUCE) return fail(MOX_ENOMEM, "a reduce partition holds more distinct words than it can split by hash");

@@ -32,20 +32,21 @@ def mixed_corpus(n, seed):
     return z[: n // 2] + b" " + u + b"\n" + extra + b" " + z[n // 2:]
 
 
-def run_ranks(data, world, gather_root=None, lib_path=None, stats=None, flags=0, table_order=False):
+def run_ranks(data, world, gather_root=None, lib_path=None, stats=None, flags=0, table_order=False, reserve_bytes=0):
     """Each rank: engine on device 0, its shard, exchange over ThreadAlltoall;
     with gather_root, then the gather of every table into that rank's engine
     (out[root] is then the gathered table, the others their own).  lib_path:
     a check build; stats: a list that receives every rank's mox_stats; flags:
     the engines' flags (MOX_F_SORT_BYTES: the sorted exchange); table_order:
-    items in the table's own order instead of sorted."""
+    items in the table's own order instead of sorted; reserve_bytes: the
+    engines' mox_config.reserve_bytes."""
     x = mdist.ThreadAlltoall(world)
     out, errs = [None] * world, []
 
     def rank_main(r):
         try:
             lo, hi, ob, oe, at_end = mdist.shard_range(len(data), world, r)
-            e = mox.Engine(device=0, lib_path=lib_path, flags=flags)
+            e = mox.Engine(device=0, lib_path=lib_path, flags=flags, reserve_bytes=reserve_bytes)
             try:
                 buf = data[lo:hi]
                 d = e.alloc(max(1, len(buf)))
