@@ -561,9 +561,10 @@ int run_corpus(mox_engine* e, const Corpus& c) {
     if ((rc = pipeline_once(e, c))) return rc;
     const Ctl& h = *e->h_ctl;
     if (e->verbose)
-      fprintf(stderr, "[mox] attempt %d: overflow 0x%x cold_need %llu spill_need %llu w_total %llu u_n %llu n_total %llu caps cold %u spill %u w %llu run %.3f ms; units %llu, sort2 list %llu, k_reduce list %llu, k_reduce_small list %llu, split partitions %u, max sub-passes %u\n",
+      fprintf(stderr, "[mox] attempt %d: overflow 0x%x cold_need %llu spill_need %llu w_total %llu u_n %llu n_total %llu caps cold %u spill %u w %llu u %llu arena %llu long %llu table %llu bytes %llu run %.3f ms; units %llu, sort2 list %llu, k_reduce list %llu, k_reduce_small list %llu, split partitions %u, max sub-passes %u\n",
               attempt, h.overflow, h.cold_need, h.spill_need, h.w_total, h.u_n, h.n_total, e->w.cold_cap, e->w.spill_cap,
-              (unsigned long long)e->w.w_cap, e->stats.ms_run, h.n_units, h.n_mid, h.n_big, h.n_small, h.n_split, h.max_sub);
+              (unsigned long long)e->w.w_cap, (unsigned long long)e->w.u_cap, (unsigned long long)e->w.arena_cap,
+              (unsigned long long)e->w.long_cap, (unsigned long long)e->w.table_cap, (unsigned long long)e->w.bytes_cap, e->stats.ms_run, h.n_units, h.n_mid, h.n_big, h.n_small, h.n_split, h.max_sub);
 #if defined(MOX_ABLATE) || defined(MOX_STAMP)
     debug_dump(e, h);
 #endif

@@ -48,9 +48,10 @@ spill, which is correct and changes the record kinds).
 Not covered: full (h32, hash32b) collisions (the forced-collision build,
 test_gpu_collide.py); kk other than 5 and partitions near a kk boundary (kk
 follows a sampled estimate through __logf); units of more than RED_CAP keys
-inside a split partition; k_xsplit at more than 16 ranks; the long-word table;
-a map grid other than 256 workgroups (region_fill models that grid: on another
-device a spill would fail the geometry assertions, not exactness)."""
+inside a split partition; k_xsplit at more than 16 ranks; a map grid other than
+256 workgroups (region_fill models that grid: on another device a spill would
+fail the geometry assertions, not exactness).  The long-word table, the spill
+path under overflow and the buffer-growth retries: test_gpu_growth.py."""
 import os
 import re
 import subprocess
@@ -71,6 +72,12 @@ LINE = re.compile(r"^\[mox\] (reduce-only )?attempt (\d+): overflow 0x([0-9a-f]+
                   r"split partitions (\d+), max sub-passes (\d+)$", re.M)
 
 
+# the counters and capacities of a map + reduce pass's line (test_gpu_growth.py)
+CAPS = re.compile(r"cold_need (\d+) spill_need \d+ w_total (\d+) u_n (\d+) n_total (\d+) caps cold (\d+) spill (\d+) w (\d+)"
+                  r"(?: u (\d+) arena (\d+) long (\d+) table (\d+) bytes (\d+))? run ")
+CAPS_KEYS = ("cold_need", "w_total", "u_n", "n_total", "cold", "spill", "w", "u", "arena", "long", "table", "bytes")
+
+
 def attempt_lines(err, reduce_only=False):
     """The engine's MOX_VERBOSE lines of the map + reduce pass (or of the
     reduce-only pass) as dicts, in the order printed."""
@@ -78,9 +85,12 @@ def attempt_lines(err, reduce_only=False):
     for m in LINE.finditer(err):
         if bool(m.group(1)) != reduce_only:
             continue
+        c = CAPS.search(m.group(0))
         out.append({"attempt": int(m.group(2)), "overflow": int(m.group(3), 16), "spill_need": int(m.group(4) or 0),
                     "units": int(m.group(5)), "sort2": int(m.group(6)), "k_reduce": int(m.group(7)),
                     "k_reduce_small": int(m.group(8)), "split": int(m.group(9)), "max_sub": max(1, int(m.group(10)))})
+        if c:
+            out[-1].update({k: int(v) for k, v in zip(CAPS_KEYS, c.groups()) if v is not None})
     return out
 
 
