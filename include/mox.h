@@ -230,6 +230,27 @@ int mox_fetch_table(mox_engine* e, mox_table** out);
  * device scratch cannot be allocated: the table then stays in engine order
  * (mox_fetch_table with MOX_F_SORT_BYTES still sorts it, on the host). */
 int mox_sort_result(mox_engine* e);
+/* The k most frequent words of the device-resident result (after any run,
+ * mox_reduce_pairs, mox_exchange, mox_gather, mox_run_shards, mox_sort_result),
+ * selected on the GPU; only the selected words are copied to the host (the
+ * full table does not cross PCIe and no host pass runs over it).  *out is a
+ * normal mox_table (mox_table_free) of min(k, distinct words) entries, count
+ * descending, equal counts by their index in the device-resident table
+ * ascending -- mox_print_top_words' rule, so printing *out prints the lines
+ * the fetched table would.  tokens is the result's total token count, not the
+ * sum of the k counts.  Table order is the table as it lies in device memory
+ * at the call: engine order, rank order after a gather, bytewise order once
+ * the result is sorted (mox_sort_result, an earlier mox_fetch_table with
+ * MOX_F_SORT_BYTES, a ranged engine-group result).  This call never sorts the
+ * table itself, MOX_F_SORT_BYTES or not: engine order can differ from run to
+ * run among words longer than 16 bytes, so a caller who wants deterministic
+ * ties calls mox_sort_result first.  The result stays where it is (further
+ * calls with another k, mox_fetch_table, an exchange all see it unchanged).
+ * k == 0 or an empty result: an empty table.  MOX_EINVAL: k > MOX_TOP_MAX or a
+ * NULL argument; MOX_ESTATE: no run yet.  An engine group: member 0's gathered
+ * result. */
+#define MOX_TOP_MAX 4096
+int mox_top_words(mox_engine* e, size_t k, mox_table** out);
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

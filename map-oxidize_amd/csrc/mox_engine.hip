@@ -1038,6 +1038,7 @@ void mox_engine_destroy(mox_engine* e) {
   if (e->grp) group_destroy(e);  // the other members and the communicators
   xplan_free(e);
   bsort_free(e);
+  topk_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

@@ -1,6 +1,7 @@
 // Host side of libmox.so: the engine object and the helpers shared by the
 // pass driver (mox_engine.hip), the multi-GPU exchange / gather / engine group
-// (mox_multi.hip) and the device bytewise table sort (mox_bsort.hip).  Internal:
+// (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
+// device top-k (mox_topk.hip).  Internal:
 // the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -169,6 +170,7 @@ struct mox_engine {
   DevBuf g_counts, g_offs, g_bytes, g_recv;  // mox_gather (root)
   DevBuf s_counts, s_offs, s_bytes, s_tmp;    // device bytewise sort (mox_bsort.hip): output + scratch
   unsigned long long* h_bsort = nullptr;      // pinned: the sort's digit histograms + totals
+  DevBuf k_tmp, k_out;                        // device top-k (mox_topk.hip): scratch, output block
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -243,4 +245,6 @@ void xplan_free(mox_engine* e);
 // ---- mox_bsort.hip
 int bsort_table(mox_engine* e);  // the result table in bytewise order, on the device
 void bsort_free(mox_engine* e);
+// ---- mox_topk.hip
+void topk_free(mox_engine* e);
 }  // namespace mox_host

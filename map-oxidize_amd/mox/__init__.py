@@ -34,6 +34,7 @@ MOX_F_TIMING = 0x4
 MOX_F_TIMING_MAP = 0x8  # HIP events around the map kernel only
 
 UNIQUE_ID_BYTES = 128
+TOP_MAX = 4096  # MOX_TOP_MAX: the most words Engine.top_words selects
 
 
 class MoxError(RuntimeError):
@@ -174,6 +175,7 @@ def lib(path=None):
             "mox_run_wait": ([VP], I),
             "mox_fetch_table": ([VP, P(P(_Table))], I),
             "mox_sort_result": ([VP], I),
+            "mox_top_words": ([VP, sz, P(P(_Table))], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -358,6 +360,14 @@ class Engine:
     def sort_result(self):
         """Sort the device-resident result bytewise on the GPU (mox_sort_result)."""
         self._c(self._L.mox_sort_result(self._h))
+
+    def top_words(self, k=10):
+        """The k most frequent words of the device-resident result as a Table, count
+        descending, ties in the resident table's order; selected on the GPU, only
+        these words are copied (mox_top_words; k <= TOP_MAX)."""
+        t = ctypes.POINTER(_Table)()
+        self._c(self._L.mox_top_words(self._h, k, ctypes.byref(t)))
+        return Table(t, self._L)
 
     def stats(self):
         s = Stats()

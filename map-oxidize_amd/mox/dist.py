@@ -64,6 +64,25 @@ def merge_tables(parts):
     return out
 
 
+def merge_top(parts, k):
+    """Global top-k from per-rank top-k lists: ``parts[r]`` is rank r's
+    ``Engine.top_words(k)`` as a list of (word, count).  Ranks own disjoint
+    words after the exchange, so the global top-k is the top-k of the union,
+    by (count descending, rank ascending, position in the rank's list
+    ascending) -- the tie order mox_gather in rank order followed by
+    mox_top_words gives, without gathering the table.  A word in two parts is
+    an error, as in merge_tables."""
+    seen, rows = set(), []
+    for r, part in enumerate(parts):
+        for pos, (w, c) in enumerate(part):
+            if w in seen:
+                raise ValueError("word %r owned by two ranks" % (w,))
+            seen.add(w)
+            rows.append((-c, r, pos, w))
+    rows.sort(key=lambda t: t[:3])
+    return [(w, -c) for c, _, _, w in rows[:max(k, 0)]]
+
+
 class ThreadAlltoall:
     """In-process all-to-all between ``world`` threads (one engine per thread),
     for exercising the exchange with several ranks on one GPU without a process
