@@ -28,10 +28,13 @@ $(OUT)/mox_bsort.o: $(CSRC)/mox_bsort.hip $(HOST_DEPS)
 $(OUT)/mox_topk.o: $(CSRC)/mox_topk.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
+$(OUT)/mox_text.o: $(CSRC)/mox_text.hip $(HOST_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
+
 $(OUT)/mox_table.o: $(CSRC)/mox_table.cpp $(CSRC)/mox_table.h
 	g++ -O3 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
 
-$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_table.o
+$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # check build: device bounds checks on every derived index (MOX_CHK, mox_internal.h);
@@ -42,7 +45,7 @@ $(OUT)/mox_kernels_check.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_internal.h Makef
 $(OUT)/mox_engine_check.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
 	$(HIPCC) $(HIPFLAGS) -DMOX_CHECK -c $< -o $@
 
-$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_table.o
+$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 check: $(OUT)/libmox_check.so
@@ -61,7 +64,7 @@ $(OUT)/mox_engine_hc.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_
 $(OUT)/mox_multi_hc.o: $(CSRC)/mox_multi.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(HC_FLAGS) -c $< -o $@
 
-$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_table.o
+$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 hc: $(OUT)/libmox_hc.so

@@ -174,8 +174,12 @@ void mox_engine_destroy(mox_engine* e);
 /* ---- drop-in for main.rs:16-22 ---- */
 /* Count words of a host buffer (copied to HBM first). */
 int mox_count(mox_engine* e, const uint8_t* text, size_t len, mox_table** out);
-/* Count words of a file (reference: split_file(path) .. reduce_phase). */
+/* Count words of a file (reference: split_file(path) .. reduce_phase):
+ * mox_run_file + mox_fetch_table. */
 int mox_count_file(mox_engine* e, const char* path, mox_table** out);
+/* mox_count_file without the fetch: the result stays on the device (for
+ * mox_write_result / mox_result_text, mox_top_words, mox_fetch_table). */
+int mox_run_file(mox_engine* e, const char* path);
 void mox_table_free(mox_table* t);
 /* Reorder a fetched table bytewise ascending (Rust String Ord) in place. */
 int mox_table_sort_bytes(mox_table* t);
@@ -251,6 +255,31 @@ int mox_sort_result(mox_engine* e);
  * result. */
 #define MOX_TOP_MAX 4096
 int mox_top_words(mox_engine* e, size_t k, mox_table** out);
+/* The device-resident result as final_result.txt text, formatted on the GPU:
+ * for each table entry i in the table's order in device memory, the word's
+ * bytes, ' ', the count in decimal, '\n'.  Byte for byte what
+ * mox_write_final_result writes from a mox_fetch_table of the same result, but
+ * only the text crosses PCIe (no counts, no offsets) and no host pass runs
+ * over the words.  mox_write_result streams the text to `path` in slices (the
+ * file is truncated on open; the next slice is rendered and copied while one
+ * is written; MOX_TEXT_SLICE=<bytes> overrides the slice size, at least 256,
+ * rounded down to a multiple of 16); mox_result_text returns the whole text in
+ * host memory (*text, *len; release it with mox_text_free; an empty result
+ * gives *len == 0 and a pointer that is still valid to free).  Both complete a
+ * pending asynchronous pass first.  Order is the table as it lies in device
+ * memory at the call (see mox_top_words); with MOX_F_SORT_BYTES an unsorted
+ * result is first sorted on the device, as mox_fetch_table does
+ * (mox_stats.ms_sort).  If that sort returns MOX_ENOMEM so does the call: the
+ * result stays in engine order and nothing is written -- fall back to
+ * mox_fetch_table + mox_write_final_result, which sort on the host.  The
+ * result stays where it is and unchanged (a later mox_fetch_table,
+ * mox_top_words, exchange or a second rendering sees the same table).  A count
+ * of 0 (mox_reduce_pairs lets one through) renders as "0".  MOX_ESTATE: no run
+ * yet; MOX_EINVAL: a NULL argument; MOX_EIO: the file cannot be opened or
+ * written.  An engine group: member 0's gathered result. */
+int mox_write_result(mox_engine* e, const char* path);
+int mox_result_text(mox_engine* e, uint8_t** text, uint64_t* len);
+void mox_text_free(uint8_t* text);
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

@@ -2,7 +2,9 @@
 // Same input default ("shakes.txt" in the working directory, main.rs:10), same
 // outputs: final_result.txt with "{word} {count}\n" lines (main.rs:170-182) and
 // "Top 10 words:" + "{word}: {count}" on stdout (main.rs:184-192).  The hot
-// section (main.rs:16-22) is one mox_count_file call on the GPU.  No
+// section (main.rs:16-22) is one mox_run_file call on the GPU; the file's text
+// is rendered there too (mox_write_result) and the ten words are selected there
+// (mox_top_words), so the table itself never reaches the host.  No
 // intermediate map files exist, so the reference's cleanup lines
 // ("Successfully deleted: ...", main.rs:194-202) are not printed.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
@@ -26,13 +28,9 @@ int main(int argc, char** argv) {
   mox_engine* e = nullptr;
   if (mox_engine_create(&cfg, &e) != MOX_OK) { fprintf(stderr, "Error: %s\n", mox_last_error()); return 1; }
   mox_table* t = nullptr;
-  int rc = mox_count_file(e, path.c_str(), &t);
-  if (rc != MOX_OK) {
-    fprintf(stderr, "Error: %s\n", mox_last_error());
-    mox_engine_destroy(e);
-    return 1;
-  }
-  rc = mox_write_final_result(t, out.c_str());
+  int rc = mox_run_file(e, path.c_str());
+  if (rc == MOX_OK) rc = mox_write_result(e, out.c_str());
+  if (rc == MOX_OK) rc = mox_top_words(e, 10, &t);
   if (rc == MOX_OK) rc = mox_print_top_words(t, 10);
   if (rc != MOX_OK) fprintf(stderr, "Error: %s\n", mox_last_error());
   mox_table_free(t);

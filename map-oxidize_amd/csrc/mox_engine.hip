@@ -1039,6 +1039,7 @@ void mox_engine_destroy(mox_engine* e) {
   xplan_free(e);
   bsort_free(e);
   topk_free(e);
+  text_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {
@@ -1253,15 +1254,11 @@ int mox_count(mox_engine* e, const uint8_t* text, size_t len, mox_table** out) {
   return mox_fetch_table(e, out);
 }
 
-int mox_count_file(mox_engine* e, const char* path, mox_table** out) {
-  if (!e || !path || !out) return fail(MOX_EINVAL, "NULL argument");
-  *out = nullptr;
+int mox_run_file(mox_engine* e, const char* path) {
+  if (!e || !path) return fail(MOX_EINVAL, "NULL argument");
   HIPCHK(hipSetDevice(e->device));
   if (int rc = drain_async(e)) return rc;
-  if (e->grp) {  // engine group: every GPU reads its own byte range of the file
-    if (int rc = group_count_file(e, path)) return rc;
-    return mox_fetch_table(e, out);
-  }
+  if (e->grp) return group_count_file(e, path);  // engine group: every GPU reads its own byte range of the file
   int fd = open(path, O_RDONLY);
   if (fd < 0) return fail(MOX_EIO, "cannot open %s: %s", path, strerror(errno));
   struct stat st;
@@ -1270,8 +1267,7 @@ int mox_count_file(mox_engine* e, const char* path, mox_table** out) {
   if (len > 2 * MAP_RANGE && file_shared_stream()) {  // big file: the map overlaps the ingest
     const int rc = run_file_overlapped(e, fd, len);
     close(fd);
-    if (rc) return rc;
-    return mox_fetch_table(e, out);
+    return rc;
   }
   int rc = stage_file_range(e, fd, 0, len);
   close(fd);
@@ -1279,6 +1275,13 @@ int mox_count_file(mox_engine* e, const char* path, mox_table** out) {
   const double h2d = e->stats.ms_h2d;
   if ((rc = mox_run_range(e, len ? (const void*)e->d_text : nullptr, len, 0, len, 1))) return rc;
   e->stats.ms_h2d = h2d;  // file read + copy wall time (PCIe-inclusive ingest)
+  return MOX_OK;
+}
+
+int mox_count_file(mox_engine* e, const char* path, mox_table** out) {
+  if (!e || !path || !out) return fail(MOX_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (int rc = mox_run_file(e, path)) return rc;
   return mox_fetch_table(e, out);
 }
 

@@ -1,8 +1,8 @@
 // Host side of libmox.so: the engine object and the helpers shared by the
 // pass driver (mox_engine.hip), the multi-GPU exchange / gather / engine group
 // (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
-// device top-k (mox_topk.hip).  Internal:
-// the public interface is include/mox.h.
+// device top-k (mox_topk.hip) and the device text rendering (mox_text.hip).
+// Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -171,6 +171,10 @@ struct mox_engine {
   DevBuf s_counts, s_offs, s_bytes, s_tmp;    // device bytewise sort (mox_bsort.hip): output + scratch
   unsigned long long* h_bsort = nullptr;      // pinned: the sort's digit histograms + totals
   DevBuf k_tmp, k_out;                        // device top-k (mox_topk.hip): scratch, output block
+  // device text rendering (mox_text.hip): scanned tile lengths, two device slices,
+  // their pinned host copies and the events "slice copied"
+  DevBuf tx_pre, tx_slice[2], tx_pin[2];
+  hipEvent_t tx_ev[2]{};
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -247,4 +251,6 @@ int bsort_table(mox_engine* e);  // the result table in bytewise order, on the d
 void bsort_free(mox_engine* e);
 // ---- mox_topk.hip
 void topk_free(mox_engine* e);
+// ---- mox_text.hip
+void text_free(mox_engine* e);
 }  // namespace mox_host

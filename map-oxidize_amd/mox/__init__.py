@@ -176,6 +176,10 @@ def lib(path=None):
             "mox_fetch_table": ([VP, P(P(_Table))], I),
             "mox_sort_result": ([VP], I),
             "mox_top_words": ([VP, sz, P(P(_Table))], I),
+            "mox_write_result": ([VP, ctypes.c_char_p], I),
+            "mox_result_text": ([VP, P(P(ctypes.c_uint8)), P(U64)], I),
+            "mox_text_free": ([P(ctypes.c_uint8)], None),
+            "mox_run_file": ([VP, ctypes.c_char_p], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -338,6 +342,10 @@ class Engine:
         self._c(self._L.mox_count_file(self._h, os.fsencode(path), ctypes.byref(t)))
         return Table(t, self._L)
 
+    def run_file(self, path):
+        """count_file without the fetch: the result stays on the device (mox_run_file)."""
+        self._c(self._L.mox_run_file(self._h, os.fsencode(path)))
+
     # -- device-resident path
     def run_device(self, d_ptr, n):
         self._c(self._L.mox_run_device(self._h, ctypes.c_void_p(d_ptr), n))
@@ -368,6 +376,24 @@ class Engine:
         t = ctypes.POINTER(_Table)()
         self._c(self._L.mox_top_words(self._h, k, ctypes.byref(t)))
         return Table(t, self._L)
+
+    def write_result(self, path):
+        """The device-resident result as final_result.txt ("{word} {count}\\n" per
+        word, in the resident table's order), formatted on the GPU and streamed to
+        ``path``: what fetch().write_final_result(path) writes (mox_write_result)."""
+        self._c(self._L.mox_write_result(self._h, os.fsencode(path)))
+
+    def result_text(self):
+        """The same text as bytes (mox_result_text)."""
+        import numpy as np
+
+        p, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        self._c(self._L.mox_result_text(self._h, ctypes.byref(p), ctypes.byref(n)))
+        try:
+            # (ctypes.string_at takes a C int size: texts above 2 GiB need numpy)
+            return np.ctypeslib.as_array(p, shape=(n.value,)).tobytes() if n.value else b""
+        finally:
+            self._L.mox_text_free(p)
 
     def stats(self):
         s = Stats()
