@@ -12,7 +12,7 @@ OUT := $(PKG)/mox
 
 all: $(OUT)/libmox.so $(OUT)/libmox_corpus.so $(OUT)/meduce-gpu $(OUT)/libmox_check.so $(OUT)/libmox_hc.so oracle
 
-$(OUT)/mox_kernels.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_internal.h Makefile
+$(OUT)/mox_kernels.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSRC)/mox_internal.h Makefile
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
 HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
@@ -31,21 +31,24 @@ $(OUT)/mox_topk.o: $(CSRC)/mox_topk.hip $(HOST_DEPS)
 $(OUT)/mox_text.o: $(CSRC)/mox_text.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
+$(OUT)/mox_accum.o: $(CSRC)/mox_accum.hip $(HOST_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
+
 $(OUT)/mox_table.o: $(CSRC)/mox_table.cpp $(CSRC)/mox_table.h
 	g++ -O3 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
 
-$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_table.o
+$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # check build: device bounds checks on every derived index (MOX_CHK, mox_internal.h);
 # tests load it with MOX_LIB=.../libmox_check.so
-$(OUT)/mox_kernels_check.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_internal.h Makefile
+$(OUT)/mox_kernels_check.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSRC)/mox_internal.h Makefile
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -DMOX_CHECK -c $< -o $@
 
 $(OUT)/mox_engine_check.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
 	$(HIPCC) $(HIPFLAGS) -DMOX_CHECK -c $< -o $@
 
-$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_table.o
+$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 check: $(OUT)/libmox_check.so
@@ -55,7 +58,7 @@ check: $(OUT)/libmox_check.so
 # counters and the bounds checks (mox_internal.h, MOX_HASH_COLLIDE); tests load it
 # with mox.Engine(lib_path=...) (tests/test_gpu_collide.py)
 HC_FLAGS := -DMOX_HASH_COLLIDE -DMOX_CHECK
-$(OUT)/mox_kernels_hc.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_internal.h Makefile
+$(OUT)/mox_kernels_hc.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSRC)/mox_internal.h Makefile
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) $(HC_FLAGS) -c $< -o $@
 
 $(OUT)/mox_engine_hc.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
@@ -64,7 +67,11 @@ $(OUT)/mox_engine_hc.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_
 $(OUT)/mox_multi_hc.o: $(CSRC)/mox_multi.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(HC_FLAGS) -c $< -o $@
 
-$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_table.o
+# (the accumulator's packer hashes long words: fnv_finish must truncate there too)
+$(OUT)/mox_accum_hc.o: $(CSRC)/mox_accum.hip $(HOST_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) $(HC_FLAGS) -c $< -o $@
+
+$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum_hc.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 hc: $(OUT)/libmox_hc.so

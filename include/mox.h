@@ -280,6 +280,59 @@ int mox_top_words(mox_engine* e, size_t k, mox_table** out);
 int mox_write_result(mox_engine* e, const char* path);
 int mox_result_text(mox_engine* e, uint8_t** text, uint64_t* len);
 void mox_text_free(uint8_t* text);
+
+/* ---- accumulating results on the device (windows, chunks, many files) ---- */
+/* total += result.  Folds the device-resident result of the last run (any run,
+ * mox_reduce_pairs, exchange, gather, mox_run_shards, sorted or not) into the
+ * engine's accumulator, on the GPU; nothing is fetched.  Afterwards the engine's
+ * result IS the running total: mox_top_words, mox_write_result, mox_result_text,
+ * mox_sort_result, mox_fetch_table and (one process per rank) mox_exchange see it.
+ * The merged table is what mox_reduce_pairs gives over the two tables' rows laid
+ * end to end: words verbatim, counts summed as u64, a word of either table
+ * present (a count of 0 included), tokens the sum of both.  Order is engine
+ * order: the words of at most 16 bytes exactly as one pass over the whole input
+ * orders them, then the longer words in long-table slot order.  The first call
+ * after mox_engine_create or mox_accumulate_reset (an empty accumulator) runs no
+ * reduce: the result is saved as the total and stays the table it was.  After a
+ * merge the result is the merge pass's table, which an exchange can start from,
+ * so "accumulate the local windows, then one mox_exchange + mox_gather" works.
+ * A result is folded once: a second call without a run in between returns
+ * MOX_ESTATE and changes nothing (it would double the counts), as does a call
+ * with no result; MOX_EINVAL: a NULL engine.  The accumulator survives every
+ * later run; only the result is replaced by them.  On any error the accumulator
+ * is what it was before the call, the engine's result becomes that previous
+ * total (with an empty accumulator it is left as it was) and the run's
+ * contribution is lost: run it again and fold again.  A merge reduces the whole
+ * total again, so it costs time in the total's distinct words, not the run's.
+ * Completes pending asynchronous passes first.  An engine group folds member
+ * 0's gathered result, on member 0.
+ * MOX_TEST_FAIL_ACCUM=1 (tests; read at each call) makes a merge return
+ * MOX_ENOMEM after both tables are packed and before the reduce pass. */
+int mox_accumulate(mox_engine* e);
+/* Adds a file's counts to the accumulator in passes of about chunk_bytes
+ * (0 = the whole file in one pass, as mox_run_file; else >= 256, smaller is
+ * MOX_EINVAL).  Cut k is the first file position >= k * chunk_bytes that follows
+ * an ASCII whitespace byte (space, \t \n \v \f \r), so every chunk is a complete
+ * corpus, no token is split, and a chunk grows past chunk_bytes where the text
+ * has no ASCII whitespace; empty chunks are skipped.  Each chunk is read, run
+ * and folded (mox_accumulate); an engine group splits each chunk over its
+ * members as mox_run_file splits a file.  The call adds to whatever the
+ * accumulator holds: loop over files, mox_accumulate_reset for a fresh total.
+ * An empty file is one pass that adds nothing.  On an error the accumulator
+ * holds the chunks before the failing one (mox_accum_info.passes counts them);
+ * MOX_EUTF8 reports the byte offset in the file. */
+int mox_accumulate_file(mox_engine* e, const char* path, uint64_t chunk_bytes);
+/* Drop the accumulator and free its device memory.  The last run's result, if
+ * there is one, can be folded again afterwards (into the empty accumulator). */
+int mox_accumulate_reset(mox_engine* e);
+typedef struct mox_accum_info {
+  uint64_t passes;        /* results folded since create / reset */
+  uint64_t words;         /* distinct words of the total */
+  uint64_t tokens;        /* tokens of the total */
+  uint64_t device_bytes;  /* device memory the accumulator holds (the saved table and the packer's scratch) */
+} mox_accum_info;
+int mox_accumulate_info(const mox_engine* e, mox_accum_info* out);
+
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

@@ -7,28 +7,45 @@
 // (mox_top_words), so the table itself never reaches the host.  No
 // intermediate map files exist, so the reference's cleanup lines
 // ("Successfully deleted: ...", main.rs:194-202) are not printed.
+// Beyond the reference: every positional argument is an input file, counted
+// together (separate corpora: no token runs from one file into the next), and
+// --chunk BYTES reads each file in passes of about BYTES cut at whitespace, so
+// that neither one file nor all of them need fit in device memory.  Both go
+// through the device-resident accumulator (mox_accumulate_file); one file
+// without --chunk is the single mox_run_file call it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "mox.h"
 
 int main(int argc, char** argv) {
-  std::string path = "shakes.txt", out = "final_result.txt";
+  std::vector<std::string> paths;
+  std::string out = "final_result.txt";
   int device = -1;
+  unsigned long long chunk = 0;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
-    else path = argv[i];
+    else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) chunk = strtoull(argv[++i], nullptr, 10);
+    else paths.push_back(argv[i]);
   }
+  if (paths.empty()) paths.push_back("shakes.txt");
   mox_config cfg;
   memset(&cfg, 0, sizeof cfg);
   cfg.device = device;
   mox_engine* e = nullptr;
   if (mox_engine_create(&cfg, &e) != MOX_OK) { fprintf(stderr, "Error: %s\n", mox_last_error()); return 1; }
   mox_table* t = nullptr;
-  int rc = mox_run_file(e, path.c_str());
+  int rc = MOX_OK;
+  if (paths.size() == 1 && !chunk) {
+    rc = mox_run_file(e, paths[0].c_str());
+  } else {
+    for (size_t i = 0; i < paths.size() && rc == MOX_OK; i++) rc = mox_accumulate_file(e, paths[i].c_str(), chunk);
+  }
   if (rc == MOX_OK) rc = mox_write_result(e, out.c_str());
   if (rc == MOX_OK) rc = mox_top_words(e, 10, &t);
   if (rc == MOX_OK) rc = mox_print_top_words(t, 10);

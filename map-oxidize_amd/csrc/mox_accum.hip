@@ -1,0 +1,597 @@
+// Device-resident accumulation (mox_accumulate / mox_accumulate_file): the
+// engine's result table is folded into a running total on the GPU, so windows,
+// chunks of a file and whole files add up without a table ever reaching the
+// host ("Accumulating results").
+//
+// The total is a saved table: (counts, offs, bytes) in buffers of its own
+// (a_tab: counts, offs, bytes), copied device to device from the result after
+// every fold.  A fold is total := reduce(total rows ++ result rows): both
+// tables are packed into the exchange's receive layout for P = 2 sources
+// (source 0 the total, source 1 the result) in x_recv_short / x_recv_blob, and
+// reduce_received (mox_multi.hip), the reduce-only pass of the exchange and of
+// mox_reduce_pairs, runs over them unchanged.
+//
+// The packer takes a table in generic form (counts, offs, bytes, n): any
+// result, whatever buffers mox_engine::Res points at and whatever its order
+// (engine order, sorted, gathered), so short and long rows may interleave.  A
+// row is classified from its bytes, by reduce_pairs_impl's rule: 1..16 bytes
+// without a NUL byte -> a zero-padded WRec; every other row -> an XHdr (the
+// FNV-1a-64 of its bytes through fnv_finish, length, count, offset) plus its
+// bytes, padded to 8, in its source's blob.  Tiles of AC_TILE consecutive rows
+// (one workgroup per tile), tiles of source 0 first:
+//
+//  1. k_ac_count: per tile its short rows, long rows and padded long bytes.
+//  2. k_ac_scan (one workgroup): exclusive scans of the three tile arrays,
+//     separately per source, the six totals behind them.  One 48-byte copy to
+//     the host sizes the wire buffers and the reduce pass's Caps exactly.
+//  3. k_ac_pack: every record at its scanned position.  Rows are taken in row
+//     order (256 at a time); a row's rank among the tile's short / long rows
+//     is a ballot rank inside its wave plus the wave totals before it (LDS), and
+//     a long word's byte offset a wave scan of the padded lengths: positions
+//     are deterministic and there is no global atomic anywhere.  Long words up
+//     to AC_COOP bytes are hashed and copied by their lane; longer ones are
+//     listed in LDS and taken by whole waves afterwards: the 64 lanes load 64
+//     consecutive 8-byte words (one coalesced 512-byte run), store them, and
+//     the hash walks the words lane by lane through v_readlane.  FNV-1a is a
+//     serial recurrence (h' = (h ^ b) * P), so only the loads and stores of a
+//     word spread over the lanes; its multiply chain does not.  The hash has to
+//     be the map's own (k_map's long lane), not merely some function of the
+//     bytes: after a fold the merge pass's long table feeds mox_exchange, which
+//     picks a long word's owner rank by this hash on every rank.
+//
+// Key loads: the 16 key bytes of a row at byte offset o come from three aligned
+// 8-byte loads at o & ~7 and a funnel shift, so they read up to 23 bytes past
+// o; a long word's copy reads whole 8-byte words the same way.  Every bytes
+// buffer a result can live in carries 64 bytes of slack past the table's bytes
+// (t_bytes: realloc_sized; g_bytes: gather_impl / group_gather; s_bytes:
+// bsort_table; a_bytes: acc_reserve below), and a row starts at o <= nb, so no
+// load leaves its allocation and none is clamped.  What is read past a word is
+// masked by the word's length before the NUL test, the hash and every store.
+// A zero-length row (no result holds one) loads nothing: it becomes a header
+// with no bytes.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   k_ac_count  38 VGPRs,  55 SGPRs,    96 B LDS, no scratch, no spills (8 waves / SIMD)
+//   k_ac_scan   66 VGPRs,  75 SGPRs,   128 B LDS, no scratch, no spills
+//   k_ac_pack   80 VGPRs, 106 SGPRs, 12392 B LDS, no scratch, no spills (6 waves / SIMD)
+#include <algorithm>
+#include <cerrno>
+#include <cstdlib>
+
+#include "mox_host.h"
+
+namespace {
+
+constexpr int AC_T = 256;                  // threads of k_ac_count / k_ac_pack
+constexpr int AC_WAVES = AC_T / 64;
+constexpr int AC_PER = 4;                  // rows per thread and tile
+constexpr uint32_t AC_TILE = AC_T * AC_PER;  // rows per tile (tests/accum_cases.py TILE)
+constexpr uint32_t AC_COOP = 256;          // a longer long word is copied by a whole wave
+static_assert(AC_TILE == 1024, "tests/accum_cases.py TILE");
+
+// A table in generic form; nt = its tiles.
+struct AcTab {
+  const uint64_t* counts;
+  const uint64_t* offs;
+  const uint8_t* bytes;
+  uint64_t n, nt;
+};
+// Where the records go: source s's WRecs from shorts[sbase[s]], its headers at
+// blob + bbase[s], its word bytes behind its nlong[s] headers.
+struct AcOut {
+  mox::WRec* shorts;
+  uint8_t* blob;
+  uint64_t sbase[2], bbase[2], nlong[2];
+};
+
+constexpr uint64_t AC_FNV0 = 0xcbf29ce484222325ull;
+__device__ __forceinline__ uint64_t ac_fnv_step(uint64_t h, uint64_t b) { return (h ^ b) * 0x100000001b3ull; }
+__device__ __forceinline__ uint64_t ac_mask(uint64_t x, uint64_t n) { return n >= 8 ? x : x & ((1ull << (8 * n)) - 1ull); }
+__device__ __forceinline__ uint64_t ac_haszero(uint64_t v) { return (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull; }
+// 8-byte word i of the bytes from offset o on (q = the aligned word that holds o, sh = 8 (o & 7))
+__device__ __forceinline__ uint64_t ac_word(const uint64_t* q, uint32_t sh, uint64_t i) {
+  const uint64_t a = q[i], b = q[i + 1];
+  return sh ? (a >> sh) | (b << (64 - sh)) : a;
+}
+
+// Row classification.  len in 1..16: the key, masked by the length, and
+// whether it is NUL-free (bytes past the length are filled with ones for the
+// test).  Returns true for a short row (k0, k1 valid).
+__device__ __forceinline__ bool ac_short(const uint8_t* bytes, uint64_t o, uint64_t len, uint64_t& k0, uint64_t& k1) {
+  if (len - 1 >= 16) return false;  // 0 or > 16 bytes
+  const uint64_t* q = reinterpret_cast<const uint64_t*>(bytes + (o & ~7ull));
+  const uint32_t sh = (uint32_t)(o & 7u) * 8u;
+  const uint64_t a = q[0], b = q[1], c = q[2];
+  k0 = sh ? (a >> sh) | (b << (64 - sh)) : a;
+  k1 = sh ? (b >> sh) | (c << (64 - sh)) : b;
+  k0 = ac_mask(k0, len);
+  k1 = len > 8 ? ac_mask(k1, len - 8) : 0ull;
+  const uint64_t f0 = len >= 8 ? 0ull : ~0ull << (8 * len);
+  const uint64_t f1 = len >= 16 ? 0ull : (len <= 8 ? ~0ull : ~0ull << (8 * (len - 8)));
+  return !(ac_haszero(k0 | f0) | ac_haszero(k1 | f1));
+}
+
+__device__ __forceinline__ uint64_t ac_wave_sum64(uint64_t x) {
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+__device__ __forceinline__ uint64_t ac_wave_incscan64(uint64_t x) {
+  const int lane = threadIdx.x & 63;
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
+}  // namespace
+
+// tc[0 * nt + tile] = short rows, tc[1 * nt + tile] = long rows, tc[2 * nt +
+// tile] = padded long bytes of the tile; nt = a.nt + b.nt.
+extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(AcTab a, AcTab b, uint64_t* tc) {
+  __shared__ uint64_t s_w[AC_WAVES][3];
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t nt = a.nt + b.nt;
+  for (uint64_t tile = blockIdx.x; tile < nt; tile += gridDim.x) {
+    const bool first = tile < a.nt;
+    const AcTab& s = first ? a : b;
+    const uint64_t base = (first ? tile : tile - a.nt) * AC_TILE;
+    uint64_t ns = 0, nl = 0, lb = 0;
+#pragma unroll
+    for (int j = 0; j < AC_PER; j++) {
+      const uint64_t i = base + (uint32_t)j * AC_T + t;
+      if (i < s.n) {
+        const uint64_t o = __builtin_nontemporal_load(s.offs + i), len = __builtin_nontemporal_load(s.offs + i + 1) - o;
+        uint64_t k0, k1;
+        if (ac_short(s.bytes, o, len, k0, k1)) {
+          ns++;
+        } else {
+          nl++;
+          lb += (len + 7) & ~7ull;
+        }
+      }
+    }
+    ns = ac_wave_sum64(ns);
+    nl = ac_wave_sum64(nl);
+    lb = ac_wave_sum64(lb);
+    if (lane == 0) {
+      s_w[wv][0] = ns;
+      s_w[wv][1] = nl;
+      s_w[wv][2] = lb;
+    }
+    __syncthreads();
+    if (t < 3) {
+      uint64_t v = 0;
+      for (int k = 0; k < AC_WAVES; k++) v += s_w[k][t];
+      tc[(uint64_t)t * nt + tile] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// Exclusive scans in place of the three tile arrays, each in two segments
+// (source 0's tiles [0, nt0), source 1's [nt0, nt0 + nt1)); the totals at
+// tc[3 nt + 3 s + k], k = short rows, long rows, long bytes of source s.  One
+// workgroup, 1,024 values per step with a running carry (k_tx_scan's shape).
+// Also clears the word behind the totals, k_ac_pack's zero-count flag.
+extern "C" __global__ __launch_bounds__(1024) void k_ac_scan(uint64_t* tc, uint64_t nt0, uint64_t nt1) {
+  __shared__ uint64_t ws[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint64_t nt = nt0 + nt1;
+  for (int k = 0; k < 3; k++)
+    for (int s = 0; s < 2; s++) {
+      uint64_t* a = tc + (uint64_t)k * nt + (s ? nt0 : 0);
+      const uint64_t m = s ? nt1 : nt0;
+      uint64_t carry = 0;
+      for (uint64_t c = 0; c < m; c += 1024) {
+        const uint64_t i = c + threadIdx.x;
+        const uint64_t x = i < m ? a[i] : 0ull;
+        const uint64_t inc = ac_wave_incscan64(x);
+        if (lane == 63) ws[wv] = inc;
+        __syncthreads();
+        uint64_t pre = 0, tot = 0;
+        for (int j = 0; j < 16; j++) {
+          if (j < wv) pre += ws[j];
+          tot += ws[j];
+        }
+        if (i < m) a[i] = carry + pre + inc - x;
+        carry += tot;
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) tc[3 * nt + 3 * s + k] = carry;
+    }
+  if (threadIdx.x == 0) tc[3 * nt + 6] = 0;  // k_ac_pack's flag: a short row with count 0
+}
+
+// Every row of both tables at its scanned position (tc: k_ac_scan's output).
+// tc[3 nt + 6] is set when a short row has count 0 (such records need the
+// reduce pass's k_reduce_z; mox_kernels.hip).
+extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, uint64_t* __restrict__ tc, AcOut out) {
+  __shared__ uint64_t s_w[AC_WAVES][3];   // a round's short rows, long rows, long bytes per wave
+  __shared__ uint64_t s_big_b[AC_TILE];   // long words over AC_COOP bytes: byte offset in the source's blob area,
+  __shared__ uint16_t s_big_k[AC_TILE];   // ... row inside the tile
+  __shared__ uint16_t s_big_r[AC_TILE];   // ... and header rank inside the tile
+  __shared__ uint32_t s_nbig;
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t nt = a.nt + b.nt;
+  for (uint64_t tile = blockIdx.x; tile < nt; tile += gridDim.x) {
+    const bool first = tile < a.nt;
+    const AcTab& s = first ? a : b;
+    const int si = first ? 0 : 1;
+    const uint64_t base = (first ? tile : tile - a.nt) * AC_TILE;
+    mox::WRec* S = out.shorts + out.sbase[si] + tc[tile];
+    mox::XHdr* H = reinterpret_cast<mox::XHdr*>(out.blob + out.bbase[si]) + tc[nt + tile];
+    uint8_t* area = out.blob + out.bbase[si] + out.nlong[si] * sizeof(mox::XHdr);
+    uint64_t rs = 0, rl = 0, rb = tc[2 * nt + tile];  // running short rank, long rank, byte offset
+    if (t == 0) s_nbig = 0;
+    for (int j = 0; j < AC_PER; j++) {
+      const uint64_t i = base + (uint32_t)j * AC_T + t;
+      uint64_t o = 0, len = 0, cnt = 0, k0 = 0, k1 = 0;
+      bool is_s = false, is_l = false;
+      if (i < s.n) {
+        o = __builtin_nontemporal_load(s.offs + i);
+        len = __builtin_nontemporal_load(s.offs + i + 1) - o;
+        cnt = __builtin_nontemporal_load(s.counts + i);
+        is_s = ac_short(s.bytes, o, len, k0, k1);
+        is_l = !is_s;
+      }
+      const uint64_t ms = __ballot(is_s), ml = __ballot(is_l);
+      if (__ballot(is_s && cnt == 0) && lane == 0) tc[3 * nt + 6] = 1;
+      const uint64_t below = lane ? ~0ull >> (64 - lane) : 0ull;
+      const uint64_t pl = is_l ? (len + 7) & ~7ull : 0ull;
+      const uint64_t inc = ac_wave_incscan64(pl);
+      __syncthreads();  // the previous round's s_w has been read (and s_nbig is zero)
+      if (lane == 63) {
+        s_w[wv][0] = (uint64_t)__popcll(ms);
+        s_w[wv][1] = (uint64_t)__popcll(ml);
+        s_w[wv][2] = inc;
+      }
+      __syncthreads();
+      uint64_t ps = rs, pq = rl, pb = rb;
+      for (uint32_t k = 0; k < (uint32_t)AC_WAVES; k++) {
+        if (k < wv) {
+          ps += s_w[k][0];
+          pq += s_w[k][1];
+          pb += s_w[k][2];
+        }
+        rs += s_w[k][0];
+        rl += s_w[k][1];
+        rb += s_w[k][2];
+      }
+      if (is_s) {
+        S[ps + __popcll(ms & below)] = mox::WRec{k0, k1, cnt};
+      } else if (is_l) {
+        const uint64_t r = pq + __popcll(ml & below), bo = pb + inc - pl;
+        if (len <= AC_COOP) {  // this lane: 8-byte words, the last one masked (its pad bytes are zero)
+          const uint64_t* q = reinterpret_cast<const uint64_t*>(s.bytes + (o & ~7ull));
+          const uint32_t sh = (uint32_t)(o & 7u) * 8u;
+          uint64_t* d = reinterpret_cast<uint64_t*>(area + bo);
+          uint64_t h = AC_FNV0;
+          for (uint64_t x = 0; 8 * x < len; x++) {
+            const uint64_t m = len - 8 * x;
+            const uint64_t v = ac_mask(ac_word(q, sh, x), m);
+            d[x] = v;
+            const uint32_t nb = m < 8 ? (uint32_t)m : 8u;
+            for (uint32_t y = 0; y < nb; y++) h = ac_fnv_step(h, (v >> (8 * y)) & 0xFFu);
+          }
+          H[r] = mox::XHdr{mox::fnv_finish(h), len, cnt, bo};
+        } else {  // a whole wave below, which also writes the header
+          const uint32_t x = atomicAdd(&s_nbig, 1u);
+          s_big_b[x] = bo;
+          s_big_k[x] = (uint16_t)((uint32_t)j * AC_T + t);
+          s_big_r[x] = (uint16_t)r;  // r < AC_TILE
+        }
+      }
+    }
+    __syncthreads();
+    // long words over AC_COOP bytes: one wave each
+    const uint32_t nbig = s_nbig;
+    for (uint32_t x = wv; x < nbig; x += AC_WAVES) {
+      const uint64_t i = base + s_big_k[x];
+      const uint64_t o = s.offs[i], len = s.offs[i + 1] - o;
+      const uint64_t* q = reinterpret_cast<const uint64_t*>(s.bytes + (o & ~7ull));
+      const uint32_t sh = (uint32_t)(o & 7u) * 8u;
+      uint64_t* d = reinterpret_cast<uint64_t*>(area + s_big_b[x]);
+      const uint64_t nw = (len + 7) / 8;
+      uint64_t h = AC_FNV0;
+      for (uint64_t w0 = 0; w0 < nw; w0 += 64) {
+        const uint64_t wi = w0 + lane;
+        uint64_t v = 0;
+        if (wi < nw) {
+          v = ac_mask(ac_word(q, sh, wi), len - 8 * wi);
+          d[wi] = v;
+        }
+        const uint32_t m = (uint32_t)(nw - w0 < 64 ? nw - w0 : 64);
+        for (uint32_t l = 0; l < m; l++) {  // every lane walks the same chain: the word of lane l
+          const uint64_t u = __shfl(v, (int)l);
+          const uint64_t left = len - 8 * (w0 + l);
+          if (left >= 8) {
+#pragma unroll
+            for (uint32_t y = 0; y < 8; y++) h = ac_fnv_step(h, (u >> (8 * y)) & 0xFFu);
+          } else {
+            for (uint32_t y = 0; y < (uint32_t)left; y++) h = ac_fnv_step(h, (u >> (8 * y)) & 0xFFu);
+          }
+        }
+      }
+      if (lane == 0) H[s_big_r[x]] = mox::XHdr{mox::fnv_finish(h), len, s.counts[i], s_big_b[x]};
+    }
+    __syncthreads();  // the LDS arrays are the next tile's
+  }
+}
+
+namespace mox_host {
+
+void accum_free(mox_engine* e) {
+  for (DevBuf* b : {&e->a_tab[0], &e->a_tab[1], &e->a_tab[2], &e->a_tc}) {
+    dfree(b->p);
+    b->p = nullptr;
+    b->cap = 0;
+  }
+  if (e->h_actot) (void)hipHostFree(e->h_actot);
+  e->h_actot = nullptr;
+  e->acc = mox_engine::Acc{};
+}
+
+}  // namespace mox_host
+
+namespace {
+
+AcTab ac_tab(const uint64_t* counts, const uint64_t* offs, const uint8_t* bytes, uint64_t n) {
+  return AcTab{counts, offs, bytes, n, (n + AC_TILE - 1) / AC_TILE};
+}
+
+// The engine's result becomes the saved total (after a failed fold, and where
+// nothing else is left of the result).
+void acc_as_result(mox_engine* e) {
+  mox_engine::Res& r = e->res;
+  r.counts = (const uint64_t*)e->a_tab[0].p;
+  r.offs = (const uint64_t*)e->a_tab[1].p;
+  r.bytes = (const uint8_t*)e->a_tab[2].p;
+  r.n = e->acc.n;
+  r.nb = e->acc.nb;
+  r.tokens = e->acc.tokens;
+  r.pass = false;
+  r.exchanged = false;
+  r.sorted = e->acc.sorted;
+  r.folded = true;
+  e->have_result = true;
+}
+
+// Buffers for a total of n rows and nb bytes into b[0..2] (a_bytes' layout:
+// 64 bytes of slack for the packer's aligned loads).
+int acc_reserve(DevBuf* b, uint64_t n, uint64_t nb) {
+  int rc;
+  if ((rc = grow_dev(b[0], 8 * n + 64)) || (rc = grow_dev(b[1], 8 * (n + 1) + 64)) || (rc = grow_dev(b[2], nb + 64))) return rc;
+  return MOX_OK;
+}
+
+// total := the engine's result (device to device), into buffers dst[0..2] that hold it.
+int acc_save(mox_engine* e, DevBuf* dst) {
+  const mox_engine::Res& r = e->res;
+  hipStream_t s = e->stream;
+  if (r.n) {
+    HIPCHK(hipMemcpyAsync(dst[0].p, r.counts, 8 * r.n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(dst[1].p, r.offs, 8 * (r.n + 1), hipMemcpyDeviceToDevice, s));
+    if (r.nb) HIPCHK(hipMemcpyAsync(dst[2].p, r.bytes, r.nb, hipMemcpyDeviceToDevice, s));
+  } else {
+    HIPCHK(hipMemsetAsync(dst[1].p, 0, 8, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return MOX_OK;
+}
+
+void acc_commit(mox_engine* e, uint64_t passes) {
+  e->acc.have = true;
+  e->acc.n = e->res.n;
+  e->acc.nb = e->res.nb;
+  e->acc.tokens = e->res.tokens;
+  e->acc.sorted = e->res.sorted;
+  e->acc.passes = passes;
+  e->res.folded = true;
+}
+
+// Both tables into x_recv_short / x_recv_blob, then the reduce pass; fresh[0..2]
+// receive the new total's buffers where the old ones are too small (allocated
+// before the reduce pass, so that nothing can fail after it).
+int acc_merge(mox_engine* e, DevBuf* fresh, bool* use_fresh) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const mox_engine::Res& r = e->res;
+  const AcTab ta = ac_tab((const uint64_t*)e->a_tab[0].p, (const uint64_t*)e->a_tab[1].p, (const uint8_t*)e->a_tab[2].p, e->acc.n);
+  const AcTab tb = ac_tab(r.counts, r.offs, r.bytes, r.n);
+  const uint64_t nt = ta.nt + tb.nt;
+  hipStream_t s = e->stream;
+  const Seq q = seq_of(e);
+  int rc;
+  if (!e->h_actot) HIPCHK(hipHostMalloc((void**)&e->h_actot, 64, hipHostMallocDefault));
+  uint64_t* tot = e->h_actot;
+  for (int k = 0; k < 7; k++) tot[k] = 0;
+  if ((rc = grow_dev(e->a_tc, (3 * nt + 8) * 8))) return rc;
+  uint64_t* tc = (uint64_t*)e->a_tc.p;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(nt, 8ull * e->n_cu);
+  if (nt) {
+    hipLaunchKernelGGL(k_ac_count, dim3(grid), dim3(AC_T), 0, s, ta, tb, tc);
+    q.step("k_ac_count");
+    hipLaunchKernelGGL(k_ac_scan, dim3(1), dim3(1024), 0, s, tc, ta.nt, tb.nt);
+    q.step("k_ac_scan");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(tot, tc + 3 * nt, 48, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  // tot[3 s + k]: short rows, long rows, padded long bytes of source s
+  if (tot[0] + tot[1] != ta.n || tot[3] + tot[4] != tb.n || tot[2] > e->acc.nb + 8 * ta.n || tot[5] > r.nb + 8 * tb.n)
+    return fail(MOX_EHIP, "accumulate: inconsistent row counts (%llu + %llu of %llu, %llu + %llu of %llu)",
+                (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)ta.n, (unsigned long long)tot[3],
+                (unsigned long long)tot[4], (unsigned long long)tb.n);
+  XDir rdir{};
+  rdir.P = 2;
+  AcOut out{};
+  uint64_t rs = 0, rb = 0, r_long = 0;
+  for (int k = 0; k < 2; k++) {
+    out.sbase[k] = rs;
+    out.bbase[k] = rdir.blob[k] = rb;
+    out.nlong[k] = rdir.nlong[k] = tot[3 * k + 1];
+    rdir.hpre[k] = r_long;
+    rs += tot[3 * k];
+    r_long += tot[3 * k + 1];
+    rb += tot[3 * k + 1] * sizeof(XHdr) + tot[3 * k + 2];
+  }
+  rdir.blob[2] = rb;
+  rdir.hpre[2] = r_long;
+  if ((rc = grow_dev(e->x_recv_short, rs * sizeof(WRec) + 64)) || (rc = grow_dev(e->x_recv_blob, rb + 64))) return rc;
+  out.shorts = (WRec*)e->x_recv_short.p;
+  out.blob = (uint8_t*)e->x_recv_blob.p;
+  if (nt) {
+    hipLaunchKernelGGL(k_ac_pack, dim3(grid), dim3(AC_T), 0, s, ta, tb, tc, out);
+    q.step("k_ac_pack");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(tot + 6, tc + 3 * nt + 6, 8, hipMemcpyDeviceToHost, s));  // completed by the synchronisation below
+  }
+  // the new total has at most the rows and bytes of both tables
+  const uint64_t un = ta.n + tb.n, ub = e->acc.nb + r.nb;
+  *use_fresh = e->a_tab[0].cap < 8 * un + 64 || e->a_tab[1].cap < 8 * (un + 1) + 64 || e->a_tab[2].cap < ub + 64;
+  if (*use_fresh && (rc = acc_reserve(fresh, un, ub))) return rc;
+  HIPCHK(hipStreamSynchronize(s));  // both sources are packed: from here on the run's buffers may go
+  if (const char* f = getenv("MOX_TEST_FAIL_ACCUM"))
+    if (atoi(f)) return fail(MOX_ENOMEM, "accumulate: injected failure before the reduce pass (MOX_TEST_FAIL_ACCUM)");
+  mox_stats local = e->stats;
+  local.weighted_records = rs + r_long;
+  local.retries = 0;
+  e->stats.retries = 0;
+  e->reduce_zero = tot[6] != 0;  // a short word with count 0 in either table: k_reduce_z
+  rc = reduce_received(e, rs, rb, r_long, rdir, local, t0);
+  e->reduce_zero = false;
+  return rc;
+}
+
+int accumulate_impl(mox_engine* e) {
+  if (int rc = drain_async(e)) return rc;
+  if (!e->have_result) return fail(MOX_ESTATE, "no result to accumulate: run first");
+  if (e->res.folded) return fail(MOX_ESTATE, "the result is already part of the total: run again first");
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf* cur = e->a_tab;
+  if (!e->acc.have) {
+    // an empty total: the result is saved as it is and stays the pass's own table
+    if (int rc = acc_reserve(cur, e->res.n, e->res.nb)) return rc;
+    if (int rc = acc_save(e, cur)) return rc;
+    acc_commit(e, 1);
+    return MOX_OK;
+  }
+  DevBuf fresh[3];
+  bool use_fresh = false;
+  int rc = acc_merge(e, fresh, &use_fresh);
+  if (!rc) {
+    rc = acc_save(e, use_fresh ? fresh : cur);
+    if (!rc) {
+      if (use_fresh)
+        for (int k = 0; k < 3; k++) {
+          dfree(cur[k].p);
+          cur[k] = fresh[k];
+          fresh[k] = DevBuf{};
+        }
+      acc_commit(e, e->acc.passes + 1);
+      return MOX_OK;
+    }
+  }
+  // the total is what it was; the run's contribution is lost and the result is the total
+  const std::string msg = g_err;
+  for (DevBuf& b : fresh) dfree(b.p);
+  (void)hipStreamSynchronize(e->stream);
+  acc_as_result(e);
+  g_err = msg;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int mox_accumulate(mox_engine* e) {
+  if (!e) return fail(MOX_EINVAL, "engine is NULL");
+  return accumulate_impl(e);
+}
+
+extern "C" int mox_accumulate_reset(mox_engine* e) {
+  if (!e) return fail(MOX_EINVAL, "engine is NULL");
+  if (int rc = drain_async(e)) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  // a result that lives in the total's buffers (after a failed fold) goes with them
+  if (e->have_result && e->res.counts == (const uint64_t*)e->a_tab[0].p && e->a_tab[0].p) e->have_result = false;
+  accum_free(e);
+  // the last run's result, if any, may be folded into the fresh total
+  e->res.folded = false;
+  return MOX_OK;
+}
+
+extern "C" int mox_accumulate_info(const mox_engine* e, mox_accum_info* out) {
+  if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
+  out->passes = e->acc.passes;
+  out->words = e->acc.n;
+  out->tokens = e->acc.tokens;
+  out->device_bytes = e->a_tab[0].cap + e->a_tab[1].cap + e->a_tab[2].cap + e->a_tc.cap;
+  return MOX_OK;
+}
+
+extern "C" int mox_accumulate_file(mox_engine* e, const char* path, uint64_t chunk_bytes) {
+  if (!e || !path) return fail(MOX_EINVAL, "NULL argument");
+  if (chunk_bytes && chunk_bytes < 256) return fail(MOX_EINVAL, "chunk_bytes %llu: 0 (the whole file) or at least 256", (unsigned long long)chunk_bytes);
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = drain_async(e)) return rc;
+  if (!chunk_bytes) {
+    if (int rc = mox_run_file(e, path)) return rc;
+    return accumulate_impl(e);
+  }
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(MOX_EIO, "cannot open %s: %s", path, strerror(errno));
+  struct stat st;
+  if (fstat(fd, &st) != 0) {
+    close(fd);
+    return fail(MOX_EIO, "cannot stat %s: %s", path, strerror(errno));
+  }
+  const uint64_t len = (uint64_t)st.st_size;
+  // cut search (ws_cuts' rule): 64 KiB windows read forward from each nominal cut
+  std::vector<uint8_t> win(1 << 16);
+  uint64_t wlo = 0, whi = 0;
+  auto byte_at = [&](uint64_t p) -> int {
+    if (p < wlo || p >= whi) {
+      const ssize_t r = pread(fd, win.data(), win.size(), (off_t)p);
+      if (r <= 0) return -1;
+      wlo = p;
+      whi = p + (uint64_t)r;
+    }
+    return win[p - wlo];
+  };
+  int rc = MOX_OK;
+  uint64_t lo = 0, k = 1;
+  for (;;) {
+    // the next cut: the first position >= k chunk_bytes after an ASCII whitespace byte, past lo
+    uint64_t hi = len;
+    while (len && k <= (len - 1) / chunk_bytes) {
+      uint64_t p = std::max(k * chunk_bytes, lo);
+      k++;
+      while (p < len) {
+        const int b = byte_at(p - 1);
+        if (b < 0) { rc = fail(MOX_EIO, "cannot read %s: %s", path, strerror(errno)); break; }
+        if (b == ' ' || (b >= 9 && b <= 13)) break;
+        p++;
+      }
+      if (rc || p >= len) break;
+      if (p > lo) { hi = p; break; }
+    }
+    if (rc) break;
+    const uint64_t n = hi - lo;
+    if (e->grp) {
+      rc = group_count_fd(e, fd, lo, n);  // the chunk split over the members, as mox_run_file splits a file
+    } else {
+      rc = stage_file_range(e, fd, lo, n);
+      if (!rc) {
+        rc = mox_run_range(e, n ? (const void*)e->d_text : nullptr, n, 0, n, 1);
+        if (rc == MOX_EUTF8 && e->h_ctl->err_utf8 != ~0ull)  // the reference's InvalidData: the file's offset
+          rc = fail(MOX_EUTF8, "stream did not contain valid UTF-8 (byte %llu)", (unsigned long long)(lo + e->h_ctl->err_utf8));
+      }
+    }
+    if (!rc) rc = accumulate_impl(e);
+    if (rc || hi >= len) break;
+    lo = hi;
+  }
+  close(fd);
+  return rc;
+}

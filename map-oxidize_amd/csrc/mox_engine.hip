@@ -285,7 +285,7 @@ void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q) {
   q.step("k_reduce_sort1");
   hipLaunchKernelGGL(k_reduce_sort2, dim3(8 * e->n_cu), dim3(64), 0, s, w);  // one wave per unit of 513..1024 records
   q.step("k_reduce_sort2");
-  hipLaunchKernelGGL(k_reduce, dim3(NB), dim3(RED_THREADS), reduce_lds_bytes(), s, w);  // workgroup b: partition b, then the work list
+  hipLaunchKernelGGL(e->reduce_zero ? k_reduce_z : k_reduce, dim3(NB), dim3(RED_THREADS), reduce_lds_bytes(), s, w);  // workgroup b: partition b, then the work list
   q.step("k_reduce");
   hipLaunchKernelGGL(k_reduce_small, dim3(8 * e->n_cu), dim3(128), 0, s, w);  // persistent, 8 per CU (SR_THREADS)
   q.step("k_reduce_small");
@@ -446,6 +446,7 @@ void set_result(mox_engine* e, const Ctl& h) {
   e->res.pass = true;
   e->res.exchanged = false;
   e->res.sorted = false;
+  e->res.folded = false;
   e->have_result = true;
 }
 
@@ -720,7 +721,8 @@ int engine_create_one(const mox_config* cfg, int dev, mox_engine** out) {
     return fail(MOX_EHIP, "side stream / events: creation failed");
   }
   if (hipFuncSetAttribute((const void*)k_map, hipFuncAttributeMaxDynamicSharedMemorySize, (int)map_lds_bytes()) != hipSuccess ||
-      hipFuncSetAttribute((const void*)k_reduce, hipFuncAttributeMaxDynamicSharedMemorySize, (int)reduce_lds_bytes()) != hipSuccess) {
+      hipFuncSetAttribute((const void*)k_reduce, hipFuncAttributeMaxDynamicSharedMemorySize, (int)reduce_lds_bytes()) != hipSuccess ||
+      hipFuncSetAttribute((const void*)k_reduce_z, hipFuncAttributeMaxDynamicSharedMemorySize, (int)reduce_lds_bytes()) != hipSuccess) {
     mox_engine_destroy(e);
     return fail(MOX_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
   }
@@ -1040,6 +1042,7 @@ void mox_engine_destroy(mox_engine* e) {
   bsort_free(e);
   topk_free(e);
   text_free(e);
+  accum_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

@@ -1,7 +1,8 @@
 // Host side of libmox.so: the engine object and the helpers shared by the
 // pass driver (mox_engine.hip), the multi-GPU exchange / gather / engine group
 // (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
-// device top-k (mox_topk.hip) and the device text rendering (mox_text.hip).
+// device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
+// the device-resident accumulator (mox_accum.hip).
 // Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -43,6 +44,7 @@ __global__ void k_unicode(Corpus c, Work w, Tables T);
 __global__ void k_hist(Work w);
 __global__ void k_scatter(Work w);
 __global__ void k_reduce(Work w);
+__global__ void k_reduce_z(Work w);
 __global__ void k_split_count(Work w);
 __global__ void k_unit_scan(Work w);
 __global__ void k_split_scatter(Work w);
@@ -166,7 +168,18 @@ struct mox_engine {
     bool pass = false;       // true: the t_* buffers of the last pass (an exchange can start from it)
     bool exchanged = false;  // true: the final table of an exchange (this rank's words are final: gatherable)
     bool sorted = false;     // true: in bytewise order (bsort_table)
+    bool folded = false;     // true: already part of the accumulator (mox_accumulate takes a result once)
   } res;
+  // mox_accumulate (mox_accum.hip): the running total as a saved table (a_tab:
+  // counts, offs, bytes; 64 bytes of slack each), the packer's tile counts and
+  // their pinned totals
+  struct Acc {
+    bool have = false, sorted = false;
+    uint64_t n = 0, nb = 0, tokens = 0, passes = 0;
+  } acc;
+  DevBuf a_tab[3], a_tc;
+  uint64_t* h_actot = nullptr;
+  bool reduce_zero = false;  // the reduce-only pass being launched holds weighted records with count 0: k_reduce_z
   DevBuf g_counts, g_offs, g_bytes, g_recv;  // mox_gather (root)
   DevBuf s_counts, s_offs, s_bytes, s_tmp;    // device bytewise sort (mox_bsort.hip): output + scratch
   unsigned long long* h_bsort = nullptr;      // pinned: the sort's digit histograms + totals
@@ -245,6 +258,9 @@ void group_destroy(mox_engine* e);
 int group_create(mox_engine* e, const mox_config* cfg);
 int group_count_host(mox_engine* e, const uint8_t* text, size_t len);
 int group_count_file(mox_engine* e, const char* path);
+int group_count_fd(mox_engine* e, int fd, uint64_t off, uint64_t len);  // bytes [off, off + len) of an open file
+int reduce_received(mox_engine* e, uint64_t rs, uint64_t rb, uint64_t r_long, const XDir& rdir, const mox_stats& local,
+                    std::chrono::steady_clock::time_point t0);
 void xplan_free(mox_engine* e);
 // ---- mox_bsort.hip
 int bsort_table(mox_engine* e);  // the result table in bytewise order, on the device
@@ -253,4 +269,6 @@ void bsort_free(mox_engine* e);
 void topk_free(mox_engine* e);
 // ---- mox_text.hip
 void text_free(mox_engine* e);
+// ---- mox_accum.hip
+void accum_free(mox_engine* e);
 }  // namespace mox_host

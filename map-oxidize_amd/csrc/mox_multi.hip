@@ -498,6 +498,7 @@ int gather_impl(mox_engine* e, int P, int me, int root, Transport& T) {
     e->res.pass = false;
     e->res.exchanged = false;  // gathered: final, not gathered again
     e->res.sorted = all_sorted && e->xp && e->xp->ranged;
+    e->res.folded = false;
   } else {
     HIPCHK(hipStreamSynchronize(s));  // the send buffer is reused by the next exchange
     e->res.exchanged = false;  // sent to the root: a table takes part in one gather
@@ -833,6 +834,7 @@ int group_gather(Group& G) {
   res.pass = false;
   res.exchanged = false;
   res.sorted = all_sorted;
+  res.folded = false;
   root->have_result = true;
   root->stats.gather_bytes = recv_bytes;
   return MOX_OK;
@@ -961,7 +963,6 @@ int group_count_host(mox_engine* e, const uint8_t* text, size_t len) {
 // Each member reads its own byte range of the file (its reader threads,
 // pinned buffers and streams) into its GPU: 8 x n_gpus reads in flight.
 int group_count_file(mox_engine* e, const char* path) {
-  Group& G = *e->grp;
   const int fd = open(path, O_RDONLY);
   if (fd < 0) return fail(MOX_EIO, "cannot open %s: %s", path, strerror(errno));
   struct stat st;
@@ -969,11 +970,20 @@ int group_count_file(mox_engine* e, const char* path) {
     close(fd);
     return fail(MOX_EIO, "cannot stat %s: %s", path, strerror(errno));
   }
-  const uint64_t len = (uint64_t)st.st_size;
+  const int rc = group_count_fd(e, fd, 0, (uint64_t)st.st_size);
+  close(fd);
+  return rc;
+}
+
+// The same over bytes [off, off + len) of an open file, a complete corpus of
+// its own (mox_accumulate_file's chunks); an error offset is the file's.
+int group_count_fd(mox_engine* e, int fd, uint64_t off, uint64_t len) {
+  Group& G = *e->grp;
   // cut search: 64 KiB windows read forward from each nominal cut
   std::vector<uint8_t> win(1 << 16);
   uint64_t wlo = 0, whi = 0;
   auto byte_at = [&](uint64_t p) -> int {
+    p += off;
     if (p < wlo || p >= whi) {
       const ssize_t r = pread(fd, win.data(), win.size(), (off_t)p);
       if (r <= 0) return -1;
@@ -982,10 +992,10 @@ int group_count_file(mox_engine* e, const char* path) {
     }
     return win[p - wlo];
   };
-  const std::vector<uint64_t> cut = ws_cuts(len, G.n, byte_at);
+  std::vector<uint64_t> cut = ws_cuts(len, G.n, byte_at);
+  for (uint64_t& c : cut) c += off;
   const auto t0 = std::chrono::steady_clock::now();
   int rc = for_members(G, [&](int i) { return stage_file_range(G.m[i], fd, cut[i], cut[i + 1] - cut[i]); });
-  close(fd);
   if (rc) return rc;
   const double ms_ingest = ms_since(t0);
   std::vector<Corpus> c(G.n);
@@ -1066,6 +1076,7 @@ int reduce_pairs_impl(mox_engine* e, const uint8_t* bytes, const uint64_t* offs,
   std::vector<XHdr> hdrs;
   std::vector<uint8_t> lbytes;
   shorts.reserve(n);
+  bool zero = false;  // a short word with count 0: the reduce pass takes k_reduce_z (mox_kernels.hip)
   for (uint64_t i = 0; i < n; i++) {
     const uint64_t a = offs[i], len = offs[i + 1] - offs[i];
     if (offs[i + 1] < a) return fail(MOX_EINVAL, "offs not ascending at %llu", (unsigned long long)i);
@@ -1078,6 +1089,7 @@ int reduce_pairs_impl(mox_engine* e, const uint8_t* bytes, const uint64_t* offs,
       memcpy(&r.w0, k, 8);
       memcpy(&r.w1, k + 8, 8);
       r.count = counts[i];
+      zero = zero || r.count == 0;
       shorts.push_back(r);
     } else {
       uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a 64 (any hash works: all long words of this pass use it)
@@ -1110,7 +1122,10 @@ int reduce_pairs_impl(mox_engine* e, const uint8_t* bytes, const uint64_t* offs,
   rdir.hpre[1] = r_long;
   mox_stats local{};
   local.weighted_records = rs + r_long;
-  return reduce_received(e, rs, rb, r_long, rdir, local, t0);
+  e->reduce_zero = zero;
+  rc = reduce_received(e, rs, rb, r_long, rdir, local, t0);
+  e->reduce_zero = false;
+  return rc;
 }
 
 }  // namespace mox_host

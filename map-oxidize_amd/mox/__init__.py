@@ -81,6 +81,16 @@ class Shard(ctypes.Structure):
     ]
 
 
+class AccumInfo(ctypes.Structure):
+    """mox_accum_info: the accumulator's folds, distinct words, tokens and device bytes."""
+    _fields_ = [
+        ("passes", ctypes.c_uint64),
+        ("words", ctypes.c_uint64),
+        ("tokens", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+    ]
+
+
 class _Table(ctypes.Structure):
     _fields_ = [
         ("n", ctypes.c_uint64),
@@ -180,6 +190,10 @@ def lib(path=None):
             "mox_result_text": ([VP, P(P(ctypes.c_uint8)), P(U64)], I),
             "mox_text_free": ([P(ctypes.c_uint8)], None),
             "mox_run_file": ([VP, ctypes.c_char_p], I),
+            "mox_accumulate": ([VP], I),
+            "mox_accumulate_file": ([VP, ctypes.c_char_p, U64], I),
+            "mox_accumulate_reset": ([VP], I),
+            "mox_accumulate_info": ([VP, P(AccumInfo)], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -395,6 +409,28 @@ class Engine:
         finally:
             self._L.mox_text_free(p)
 
+    # -- accumulating results on the device (mox_accumulate*)
+    def accumulate(self):
+        """total += result: fold the device-resident result of the last run into the
+        engine's accumulator on the GPU; the result is then the running total
+        (mox_accumulate).  A result folds once: MOX_ESTATE the second time."""
+        self._c(self._L.mox_accumulate(self._h))
+
+    def accumulate_file(self, path, chunk_bytes=0):
+        """Add a file's counts to the accumulator in passes of about chunk_bytes, cut
+        at ASCII whitespace (0: the whole file in one pass; mox_accumulate_file)."""
+        self._c(self._L.mox_accumulate_file(self._h, os.fsencode(path), chunk_bytes))
+
+    def accumulate_reset(self):
+        """Drop the accumulator and free its device memory (mox_accumulate_reset)."""
+        self._c(self._L.mox_accumulate_reset(self._h))
+
+    def accumulate_info(self):
+        """{"passes", "words", "tokens", "device_bytes"} of the accumulator."""
+        a = AccumInfo()
+        self._c(self._L.mox_accumulate_info(self._h, ctypes.byref(a)))
+        return {k: int(getattr(a, k)) for k, _ in a._fields_}
+
     def stats(self):
         s = Stats()
         self._c(self._L.mox_get_stats(self._h, ctypes.byref(s)))
@@ -516,5 +552,22 @@ def count_words(data, **kw):
             return t.as_dict()
         finally:
             t.close()
+    finally:
+        e.close()
+
+
+def count_files(paths, chunk_bytes=0, **kw):
+    """One-shot: the word counts of several files together, as a Table.  Every
+    file is added to one device-resident accumulator (Engine.accumulate_file, in
+    passes of about chunk_bytes; 0: one pass per file), so the files need not fit
+    in device memory together and only the final table is fetched.  Files are
+    separate corpora: a token never continues from one file into the next."""
+    e = Engine(**kw)
+    try:
+        for p in paths:
+            e.accumulate_file(p, chunk_bytes)
+        if e.accumulate_info()["passes"] == 0:  # no files: the empty table
+            return e.count(b"")
+        return e.fetch()
     finally:
         e.close()
