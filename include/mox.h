@@ -333,6 +333,54 @@ typedef struct mox_accum_info {
 } mox_accum_info;
 int mox_accumulate_info(const mox_engine* e, mox_accum_info* out);
 
+/* ---- looking words up in the device-resident result ---- */
+/* The counts of n given words in the device-resident result, read on the GPU:
+ * only the query words go to the device and only n counts (and n indices) come
+ * back; the table is not fetched and no host pass runs over it.  Query word i
+ * is bytes[offs[i], offs[i+1]) and is taken verbatim, as mox_reduce_pairs takes
+ * its words: not lowercased, not validated as UTF-8.  A run's table holds
+ * lowercased words (Rust str::to_lowercase), so a caller who asks about text
+ * lowercases the word by Rust's rule first; "The" is not in a run's table.
+ * counts[i]: the word's count, 0 when the result does not hold the word.
+ * index[i] (index may be NULL): the word's position in the table as it lies in
+ * device memory at the call -- table order as mox_top_words defines it: engine
+ * order, rank order after a gather, bytewise order once sorted -- or
+ * MOX_LOOKUP_NONE when the word is absent.  A word the result holds with count
+ * 0 (only mox_reduce_pairs input produces one) gives counts[i] == 0 and a real
+ * index: the index tells it from an absent word.  A word that occurs several
+ * times among the queries gets the full count and the same index at every
+ * position.  info may be NULL.  With n == 0 counts, bytes and offs may be NULL
+ * too, and nothing runs on the device.
+ * Works on every form of result: after any run, mox_reduce_pairs, mox_exchange
+ * (this rank's words: ranks own disjoint words, so the ranks' counts add up to
+ * the global ones without a gather), mox_gather, mox_run_shards,
+ * mox_sort_result, mox_accumulate (the running total), a MOX_F_SORT_BYTES
+ * fetch; an engine group: member 0's gathered result.  Completes pending
+ * asynchronous passes first.  The call only reads: result, accumulator, folded
+ * and sorted state are unchanged, and a later fetch, top-k, rendering,
+ * accumulate or exchange sees what it would have seen without it.
+ * Cost: one pass over the result's offsets, and over the bytes of the words
+ * whose length some query has; device scratch is O(n + query bytes), lives in
+ * the engine and is freed by mox_engine_destroy.
+ * MOX_ESTATE: no result yet.  MOX_EINVAL: a NULL engine, a NULL required
+ * pointer, n > MOX_LOOKUP_MAX, offsets that decrease, or offs[n] - offs[0] >=
+ * 2^32 query bytes.  After any error the engine is usable and counts, index
+ * and info are untouched: they are written only once the whole call has
+ * succeeded, and then completely.
+ * MOX_LOOKUP_GRID=<workgroups> (tests; read at each call) caps the grid of the
+ * pass over the result, so that a small table runs several grid strides. */
+#define MOX_LOOKUP_MAX (1u << 20)          /* query words per call */
+#define MOX_LOOKUP_NONE (~0ull)            /* index of a word the result does not hold */
+typedef struct mox_lookup_info {
+  uint64_t queries;       /* n */
+  uint64_t distinct;      /* distinct query words */
+  uint64_t found;         /* query positions whose word the result holds */
+  uint64_t tag_mismatch;  /* probes where the hash tag was equal and the bytes differed */
+  uint64_t reserved[4];
+} mox_lookup_info;
+int mox_lookup_words(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n,
+                     uint64_t* counts, uint64_t* index, mox_lookup_info* info);
+
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

@@ -13,6 +13,10 @@
 // that neither one file nor all of them need fit in device memory.  Both go
 // through the device-resident accumulator (mox_accumulate_file); one file
 // without --chunk is the single mox_run_file call it always was.
+// --word W (repeatable) prints, after the top-10 block, "Counts:" and one
+// "{word}: {count}" line per W in argument order, read from the device-resident
+// result (mox_lookup_words).  W is taken verbatim: the table holds lowercased
+// words, so "The" counts 0.  Without --word the output is what it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
@@ -27,10 +31,12 @@ int main(int argc, char** argv) {
   std::string out = "final_result.txt";
   int device = -1;
   unsigned long long chunk = 0;
+  std::vector<std::string> words;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
     else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) chunk = strtoull(argv[++i], nullptr, 10);
+    else if (!strcmp(argv[i], "--word") && i + 1 < argc) words.push_back(argv[++i]);
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) paths.push_back("shakes.txt");
@@ -49,6 +55,19 @@ int main(int argc, char** argv) {
   if (rc == MOX_OK) rc = mox_write_result(e, out.c_str());
   if (rc == MOX_OK) rc = mox_top_words(e, 10, &t);
   if (rc == MOX_OK) rc = mox_print_top_words(t, 10);
+  if (rc == MOX_OK && !words.empty()) {
+    std::string bytes;
+    std::vector<uint64_t> offs(1, 0), counts(words.size());
+    for (const std::string& w : words) {
+      bytes += w;
+      offs.push_back(bytes.size());
+    }
+    rc = mox_lookup_words(e, (const uint8_t*)bytes.data(), offs.data(), words.size(), counts.data(), nullptr, nullptr);
+    if (rc == MOX_OK) {
+      printf("Counts:\n");
+      for (size_t i = 0; i < words.size(); i++) printf("%s: %llu\n", words[i].c_str(), (unsigned long long)counts[i]);
+    }
+  }
   if (rc != MOX_OK) fprintf(stderr, "Error: %s\n", mox_last_error());
   mox_table_free(t);
   mox_engine_destroy(e);

@@ -1043,6 +1043,7 @@ void mox_engine_destroy(mox_engine* e) {
   topk_free(e);
   text_free(e);
   accum_free(e);
+  lookup_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

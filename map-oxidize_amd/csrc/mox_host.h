@@ -2,7 +2,8 @@
 // pass driver (mox_engine.hip), the multi-GPU exchange / gather / engine group
 // (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
-// the device-resident accumulator (mox_accum.hip).
+// the device-resident accumulator (mox_accum.hip) and the device lookup
+// (mox_lookup.hip).
 // Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -188,6 +189,9 @@ struct mox_engine {
   // their pinned host copies and the events "slice copied"
   DevBuf tx_pre, tx_slice[2], tx_pin[2];
   hipEvent_t tx_ev[2]{};
+  // device lookup (mox_lookup.hip): scratch (outputs, query words, their hash set),
+  // the pinned block the offsets go up and the outputs come back through
+  DevBuf l_tmp, l_pin;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -271,4 +275,6 @@ void topk_free(mox_engine* e);
 void text_free(mox_engine* e);
 // ---- mox_accum.hip
 void accum_free(mox_engine* e);
+// ---- mox_lookup.hip
+void lookup_free(mox_engine* e);
 }  // namespace mox_host

@@ -35,6 +35,8 @@ MOX_F_TIMING_MAP = 0x8  # HIP events around the map kernel only
 
 UNIQUE_ID_BYTES = 128
 TOP_MAX = 4096  # MOX_TOP_MAX: the most words Engine.top_words selects
+LOOKUP_MAX = 1 << 20  # MOX_LOOKUP_MAX: the most words one Engine.lookup call takes
+LOOKUP_NONE = (1 << 64) - 1  # MOX_LOOKUP_NONE: the index of a word the result does not hold
 
 
 class MoxError(RuntimeError):
@@ -88,6 +90,17 @@ class AccumInfo(ctypes.Structure):
         ("words", ctypes.c_uint64),
         ("tokens", ctypes.c_uint64),
         ("device_bytes", ctypes.c_uint64),
+    ]
+
+
+class LookupInfo(ctypes.Structure):
+    """mox_lookup_info: queries, distinct query words, found positions, equal-tag byte mismatches."""
+    _fields_ = [
+        ("queries", ctypes.c_uint64),
+        ("distinct", ctypes.c_uint64),
+        ("found", ctypes.c_uint64),
+        ("tag_mismatch", ctypes.c_uint64),
+        ("reserved", ctypes.c_uint64 * 4),
     ]
 
 
@@ -194,6 +207,7 @@ def lib(path=None):
             "mox_accumulate_file": ([VP, ctypes.c_char_p, U64], I),
             "mox_accumulate_reset": ([VP], I),
             "mox_accumulate_info": ([VP, P(AccumInfo)], I),
+            "mox_lookup_words": ([VP, VP, P(U64), U64, P(U64), P(U64), P(LookupInfo)], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -430,6 +444,49 @@ class Engine:
         a = AccumInfo()
         self._c(self._L.mox_accumulate_info(self._h, ctypes.byref(a)))
         return {k: int(getattr(a, k)) for k, _ in a._fields_}
+
+    # -- counts of given words (mox_lookup_words)
+    def lookup(self, words, with_index=False, with_info=False):
+        """The counts of ``words`` (an iterable of bytes; str is encoded as UTF-8) in
+        the device-resident result, as a numpy uint64 array: 0 for a word the result
+        does not hold.  Read on the GPU: only the words go up and the counts come
+        back (mox_lookup_words; at most LOOKUP_MAX words).  Words are taken
+        verbatim; a run's table holds lowercased words.  with_index adds the array
+        of table positions (LOOKUP_NONE: absent), with_info the info dict
+        {"queries", "distinct", "found", "tag_mismatch"}; with either the result
+        is a tuple in that order."""
+        from . import spill
+
+        ws = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words]
+        data, offs, _ = spill.pack_pairs(ws, [])
+        return self.lookup_packed(data, offs, with_index, with_info)
+
+    def lookup_packed(self, data, offs, with_index=False, with_info=False):
+        """lookup() over words already packed: word i is data[offs[i]:offs[i+1]]
+        (data: bytes or a numpy uint8 array, offs: uint64[n + 1])."""
+        import numpy as np
+
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.size - 1
+        if n < 0:
+            raise ValueError("offs needs n + 1 entries")
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        if n and int(offs[-1]) > buf.size:
+            raise ValueError("offsets run past the words' bytes")
+        counts = np.zeros(n, dtype=np.uint64)
+        index = np.full(n, LOOKUP_NONE, dtype=np.uint64) if with_index else None
+        info = LookupInfo()
+        U64P = ctypes.POINTER(ctypes.c_uint64)
+        self._c(self._L.mox_lookup_words(
+            self._h, ctypes.c_void_p(buf.ctypes.data if buf.size else None), offs.ctypes.data_as(U64P), n,
+            counts.ctypes.data_as(U64P), index.ctypes.data_as(U64P) if with_index else None, ctypes.byref(info)))
+        out = (counts,)
+        if with_index:
+            out += (index,)
+        if with_info:
+            out += ({k: int(getattr(info, k)) for k in ("queries", "distinct", "found", "tag_mismatch")},)
+        return out if len(out) > 1 else counts
 
     def stats(self):
         s = Stats()

@@ -83,6 +83,34 @@ def merge_top(parts, k):
     return [(w, -c) for c, _, _, w in rows[:max(k, 0)]]
 
 
+def sum_lookups(parts, found=None):
+    """Global counts from per-rank lookups: ``parts[r]`` is rank r's
+    ``Engine.lookup(words)`` of the same words after the exchange.  Ranks own
+    disjoint words then, so the element-wise sum is the count a gather followed by
+    one lookup gives, without gathering -- the lookup counterpart of merge_top.
+    Returns a numpy uint64 array; ValueError when the lengths differ.
+    ``found[r]`` (optional) is rank r's mask ``index != LOOKUP_NONE``: a word two
+    ranks both found is an error, as in merge_tables."""
+    import numpy as np
+
+    arrs = [np.asarray(p, dtype=np.uint64).reshape(-1) for p in parts]
+    if not arrs:
+        return np.zeros(0, dtype=np.uint64)
+    if any(a.size != arrs[0].size for a in arrs):
+        raise ValueError("per-rank lookups differ in length: %r" % ([a.size for a in arrs],))
+    if found is not None:
+        masks = [np.asarray(m, dtype=bool).reshape(-1) for m in found]
+        if len(masks) != len(arrs) or any(m.size != arrs[0].size for m in masks):
+            raise ValueError("found masks do not match the lookups")
+        owners = np.sum(masks, axis=0, dtype=np.int64) if masks else np.zeros(arrs[0].size, np.int64)
+        if (owners > 1).any():
+            raise ValueError("query %d found on two ranks" % int(np.argmax(owners > 1)))
+    total = np.zeros(arrs[0].size, dtype=np.uint64)
+    for a in arrs:
+        total += a
+    return total
+
+
 class ThreadAlltoall:
     """In-process all-to-all between ``world`` threads (one engine per thread),
     for exercising the exchange with several ranks on one GPU without a process
