@@ -381,6 +381,87 @@ typedef struct mox_lookup_info {
 int mox_lookup_words(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n,
                      uint64_t* counts, uint64_t* index, mox_lookup_info* info);
 
+/* ---- filtering the device-resident result ---- */
+/* Makes the device-resident result smaller, on the GPU: the words that satisfy
+ * the predicate *f, with their counts, become the engine's result.  Only the
+ * word list goes to the device and four totals come back; the table is not
+ * fetched and no host pass runs over it.  Afterwards mox_top_words,
+ * mox_write_result / mox_result_text, mox_lookup_words, mox_accumulate,
+ * mox_sort_result and mox_fetch_table work on the subset as on any result.
+ * Predicate: a word is kept when every active term holds; a zeroed mox_filter
+ * keeps everything.
+ *  - count: min_count <= count <= max_count (max_count == 0: no upper bound).
+ *    {0, 0} is "any count", so the zero-count words mox_reduce_pairs lets
+ *    through cannot be selected alone (min_count = 1 drops them).
+ *  - length in BYTES: min_len <= length <= max_len (max_len == 0: no bound).
+ *  - prefix: the word's first prefix_len bytes equal prefix[0, prefix_len),
+ *    compared bytewise; a word shorter than the prefix is dropped.
+ *  - list: MOX_FILTER_WORDS_DROP removes the listed words (a stop list; with
+ *    n_words == 0 there is no list term), MOX_FILTER_WORDS_KEEP keeps only
+ *    listed words (a vocabulary; with n_words == 0 nothing is kept).  List
+ *    words are taken verbatim, as mox_lookup_words takes its queries (not
+ *    lowercased, duplicates allowed): a run's table holds words lowercased by
+ *    Rust's rule, so lowercase the list the same way.
+ * Result: the kept words in the order they had (engine, rank or bytewise
+ * order), tokens = the sum of the kept counts.  Sorted and folded state are
+ * the source's: a subset of a sorted table is sorted, a subset of a total
+ * already folded is not folded again (mox_accumulate returns MOX_ESTATE until
+ * a run or mox_accumulate_reset).  The new result is no pass's table and no
+ * exchanged one, even when every word was kept: mox_exchange / mox_gather
+ * after a filter return MOX_ESTATE.  The accumulator is untouched.  Zero kept
+ * words give a valid empty result (n == 0), which every call accepts as it
+ * accepts the empty corpus's.  The call never sorts, MOX_F_SORT_BYTES or not.
+ * MOX_FILTER_COUNT_ONLY: only *info is produced; the result, its flags and its
+ * buffers are exactly what they were ("how many hapaxes", "how many tokens do
+ * the stop words carry").
+ * Works on every form of result: a run's, mox_reduce_pairs, exchanged,
+ * gathered, mox_run_shards, sorted, the accumulator's total, a filtered one
+ * (filtering twice equals filtering by the conjunction).  Completes pending
+ * asynchronous passes first.  An engine group: member 0's gathered result, on
+ * member 0.
+ * Distributed use: every term is per word, and after mox_exchange each word's
+ * final count lives on one rank, so ranks filter their own exchanged result
+ * and merge top lists or sum lookups as before.  A count term applied to a
+ * local, un-exchanged table filters partial counts and is wrong.
+ * info may be NULL.  Device memory: two sets of output buffers (a call writes
+ * the set the result does not live in) and O(words / 8) scratch, held by the
+ * engine until mox_engine_destroy.
+ * MOX_ESTATE: no result yet.  MOX_EINVAL: a NULL engine or filter, a NULL
+ * pointer that is needed, prefix_len > MOX_FILTER_PREFIX_MAX, n_words >
+ * MOX_LOOKUP_MAX, offsets that decrease (or 2^32 list bytes and more), an
+ * unknown mode or flag, a reserved word that is not 0.  After any error,
+ * MOX_ENOMEM for the output buffers included, the result is exactly what it
+ * was and *info is untouched.
+ * MOX_FILTER_GRID=<workgroups> (tests; read at each call) caps the grid of the
+ * two passes over the table; MOX_TEST_FAIL_FILTER=1 (tests; read at each call)
+ * returns MOX_ENOMEM after the count pass and before the output is written. */
+#define MOX_FILTER_PREFIX_MAX 16
+#define MOX_FILTER_WORDS_DROP 0u   /* listed words are removed (stop list) */
+#define MOX_FILTER_WORDS_KEEP 1u   /* only listed words survive (vocabulary) */
+#define MOX_FILTER_COUNT_ONLY 0x1u /* flags: fill info, leave the result as it is */
+typedef struct mox_filter {
+  uint64_t min_count, max_count;   /* keep min_count <= count <= max_count; max_count == 0: no upper bound */
+  uint64_t min_len, max_len;       /* word length in BYTES; max_len == 0: no upper bound */
+  const uint8_t* prefix;           /* keep words whose first prefix_len bytes equal these; */
+  uint64_t prefix_len;             /*   0: no prefix term; > MOX_FILTER_PREFIX_MAX: MOX_EINVAL */
+  const uint8_t* words;            /* word list, word i = words[word_offs[i], word_offs[i+1]), verbatim */
+  const uint64_t* word_offs;       /*   (as mox_lookup_words takes its queries; duplicates allowed) */
+  uint64_t n_words;                /*   <= MOX_LOOKUP_MAX */
+  uint32_t words_mode;             /* MOX_FILTER_WORDS_* ; DROP with n_words == 0 is "no list term" */
+  uint32_t flags;                  /* MOX_FILTER_* */
+  uint64_t reserved[4];            /* must be 0 */
+} mox_filter;
+typedef struct mox_filter_info {
+  uint64_t words_in, words_kept;
+  uint64_t tokens_in, tokens_kept; /* tokens_kept = sum of the kept counts */
+  uint64_t bytes_kept;             /* word bytes of the kept table */
+  uint64_t list_found;             /* distinct list words the result held */
+  uint64_t device_bytes;           /* device memory the filter holds after the call */
+  double ms;                       /* wall time of the call */
+  uint64_t reserved[4];
+} mox_filter_info;
+int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_info* info /* may be NULL */);
+
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

@@ -17,10 +17,17 @@
 // "{word}: {count}" line per W in argument order, read from the device-resident
 // result (mox_lookup_words).  W is taken verbatim: the table holds lowercased
 // words, so "The" counts 0.  Without --word the output is what it always was.
+// --min-count N and --stop FILE apply one filter to the device-resident result
+// (mox_filter_result) after counting and before the file, the top ten and
+// --word: words seen fewer than N times and the words of FILE go.  FILE holds
+// words split at ASCII whitespace, taken verbatim (lowercase them: the table's
+// words are).  Without these options the output is what it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -32,14 +39,38 @@ int main(int argc, char** argv) {
   int device = -1;
   unsigned long long chunk = 0;
   std::vector<std::string> words;
+  unsigned long long min_count = 0;
+  std::string stop_path;
+  bool have_stop = false;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
     else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) chunk = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--word") && i + 1 < argc) words.push_back(argv[++i]);
+    else if (!strcmp(argv[i], "--min-count") && i + 1 < argc) min_count = strtoull(argv[++i], nullptr, 10);
+    else if (!strcmp(argv[i], "--stop") && i + 1 < argc) { stop_path = argv[++i]; have_stop = true; }
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) paths.push_back("shakes.txt");
+  // the stop list: the file's words, split at ASCII whitespace
+  std::string stop_bytes;
+  std::vector<uint64_t> stop_offs(1, 0);
+  if (have_stop) {
+    std::ifstream in(stop_path, std::ios::binary);
+    if (!in) { fprintf(stderr, "Error: cannot open %s\n", stop_path.c_str()); return 1; }
+    const std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    auto is_ws = [](unsigned char c) { return c == ' ' || (c >= 9 && c <= 13); };
+    for (size_t i = 0; i < text.size();) {
+      while (i < text.size() && is_ws((unsigned char)text[i])) i++;
+      size_t j = i;
+      while (j < text.size() && !is_ws((unsigned char)text[j])) j++;
+      if (j > i) {
+        stop_bytes.append(text, i, j - i);
+        stop_offs.push_back(stop_bytes.size());
+      }
+      i = j;
+    }
+  }
   mox_config cfg;
   memset(&cfg, 0, sizeof cfg);
   cfg.device = device;
@@ -51,6 +82,16 @@ int main(int argc, char** argv) {
     rc = mox_run_file(e, paths[0].c_str());
   } else {
     for (size_t i = 0; i < paths.size() && rc == MOX_OK; i++) rc = mox_accumulate_file(e, paths[i].c_str(), chunk);
+  }
+  if (rc == MOX_OK && (min_count || have_stop)) {
+    mox_filter f;
+    memset(&f, 0, sizeof f);
+    f.min_count = min_count;
+    f.words = (const uint8_t*)stop_bytes.data();
+    f.word_offs = stop_offs.data();
+    f.n_words = stop_offs.size() - 1;
+    f.words_mode = MOX_FILTER_WORDS_DROP;
+    rc = mox_filter_result(e, &f, nullptr);
   }
   if (rc == MOX_OK) rc = mox_write_result(e, out.c_str());
   if (rc == MOX_OK) rc = mox_top_words(e, 10, &t);

@@ -1044,6 +1044,7 @@ void mox_engine_destroy(mox_engine* e) {
   text_free(e);
   accum_free(e);
   lookup_free(e);
+  filter_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

@@ -1,0 +1,486 @@
+// Device filter (mox_filter_result): the device-resident result made smaller
+// on the GPU, so that a stop list, a count threshold, a length range or a
+// prefix is applied without fetching the table ("Filtering the
+// result").  The kept words, with their counts and in the order they had,
+// become the engine's result; only the word list goes up and four totals come
+// back.
+//
+// A stable stream compaction of (counts, offs, bytes), written against
+// mox_engine::Res in generic form: any result, whatever buffers it lives in and
+// whatever its order.  Rows go in tiles of FL_TILE consecutive rows, one
+// workgroup per tile, grid-stride; a tile is 16 wave steps of 64 consecutive
+// rows.  Positions come from scans only -- no global atomic decides where a row
+// lands -- so the output is a pure function of the table and the predicate.
+//
+//  1. k_fl_mark (only with a word list): the table index of every list word
+//     comes from the lookup (mox_lookup.hip: lookup_device leaves its index
+//     array in device memory, nothing sized by the table comes down); one bit
+//     per found index is set in an n-bit bitmap.  list_found counts the bits
+//     that were newly set, which is the number of bits set.
+//  2. k_fl_count: per row the count term, the length term (from the two
+//     offsets alone), the bitmap, then the prefix.  The prefix is the only
+//     term that touches the word bytes and is evaluated only for rows that
+//     passed the others: the 16 bytes from the row's offset on, in one load,
+//     masked to the prefix length.  The keep mask is stored, one ballot word
+//     per wave step (bit i of the mask = row i), so that the emit pass does not
+//     read word bytes again to decide.  Per tile: kept rows, kept bytes, kept
+//     count sum.
+//  3. k_fl_scan (one workgroup): exclusive scans of the three tile arrays, the
+//     totals behind them (k_ac_scan's shape).  One 32-byte copy to the host
+//     sizes the output; MOX_FILTER_COUNT_ONLY ends here.
+//  4. k_fl_emit: a kept row's output index is its tile's scanned base, plus
+//     the wave totals before it (LDS), plus its ballot rank; its byte offset
+//     the tile's byte base plus a wave scan of the kept lengths.  It writes the
+//     count, the offset and the word's bytes; offs[kept] = bytes_kept closes
+//     the table.  A tile that keeps nothing is skipped.  Words of up to
+//     FL_LANE_MAX bytes are copied by their lane; longer ones (a table word
+//     reaches 16 MiB) are listed in LDS and copied by whole waves afterwards,
+//     64 consecutive 8-byte words per step.
+//
+// Loads and stores: a word is copied as 8-byte words from its first byte on
+// (any alignment on either side), then a tail of 4, 2 and 1 bytes, so nothing
+// is read or written past a word: neighbouring output words belong to other
+// lanes.  Only the prefix load reads past a word, up to 15 bytes behind a
+// 1-byte last word; every bytes buffer a result can live in carries 64 bytes
+// of slack (see mox_accum.hip), the filter's own output buffers included, and
+// what is read past the prefix length is masked.
+//
+// Output: two sets of three buffers (mox_engine::f_tab); a call writes the set
+// the result does not live in, so a filtered result can be filtered again, and
+// e->res is repointed only when everything has succeeded.  Scratch (f_tmp) is
+// O(n / 8): three tile arrays, the keep mask and the list bitmap.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   k_fl_mark   12 VGPRs, 26 SGPRs,     4 B LDS, no scratch, no spills (8 waves / SIMD)
+//   k_fl_count  43 VGPRs, 90 SGPRs,    96 B LDS, no scratch, no spills (8 waves / SIMD)
+//   k_fl_scan  124 VGPRs, 72 SGPRs,   384 B LDS, no scratch, no spills (one workgroup)
+//   k_fl_emit   98 VGPRs, 74 SGPRs, 10312 B LDS, no scratch, no spills (4 waves / SIMD)
+#include <algorithm>
+#include <cstdlib>
+
+#include "mox_host.h"
+
+namespace {
+
+constexpr int FL_T = 256;                    // threads of k_fl_mark / k_fl_count / k_fl_emit
+constexpr int FL_WAVES = FL_T / 64;
+constexpr int FL_PER = 4;                    // rows per thread and tile
+constexpr uint32_t FL_TILE = FL_T * FL_PER;  // rows per tile (tests/filter_cases.py TILE)
+constexpr uint32_t FL_STEPS = FL_TILE / 64;  // keep-mask words per tile
+constexpr uint32_t FL_LANE_MAX = 64;         // a longer word is copied by a whole wave
+constexpr int FL_SCAN_PER = 4;               // k_fl_scan: consecutive tiles per thread ...
+constexpr uint32_t FL_SCAN_STEP = 1024 * FL_SCAN_PER;  // ... and tiles per step of its one workgroup
+static_assert(FL_TILE == 1024, "tests/filter_cases.py TILE");
+static_assert(FL_TILE <= 65536, "s_big_k holds 16-bit rows");
+static_assert(MOX_FILTER_PREFIX_MAX == 16, "the prefix is two 8-byte words");
+
+// The result in generic form (mox_engine::Res); nt = its tiles.
+struct FlTab {
+  const uint64_t* counts;
+  const uint64_t* offs;
+  const uint8_t* bytes;
+  uint64_t n, nt;
+};
+// The predicate as the kernels take it: bounds with "no upper bound" resolved,
+// the prefix as two masked 8-byte words, the list as a bitmap over table rows.
+struct FlPred {
+  uint64_t min_count, max_count, min_len, max_len;
+  uint64_t p0, p1, m0, m1, plen;
+  const uint32_t* listed;  // bit i: row i is a list word
+  uint32_t list_mode;      // 0: no list term, 1: listed rows are dropped, 2: only listed rows survive
+};
+struct FlOut {
+  uint64_t* counts;
+  uint64_t* offs;
+  uint8_t* bytes;
+  uint64_t kept, bytes_kept;
+};
+
+// loads and stores of any alignment
+struct __attribute__((packed, aligned(1))) FlKey16 {
+  uint64_t lo, hi;
+};
+struct __attribute__((packed, aligned(1))) FlU64 {
+  uint64_t v;
+};
+struct __attribute__((packed, aligned(1))) FlU32 {
+  uint32_t v;
+};
+struct __attribute__((packed, aligned(1))) FlU16 {
+  uint16_t v;
+};
+
+__device__ __forceinline__ uint64_t fl_wave_sum64(uint64_t x) {
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+__device__ __forceinline__ uint64_t fl_wave_incscan64(uint64_t x) {
+  const int lane = threadIdx.x & 63;
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+
+// d[0, len) = s[0, len), by one lane: nothing outside the two ranges is touched
+__device__ __forceinline__ void fl_copy_lane(uint8_t* d, const uint8_t* s, uint64_t len) {
+  uint64_t x = 0;
+  for (; x + 8 <= len; x += 8) reinterpret_cast<FlU64*>(d + x)->v = reinterpret_cast<const FlU64*>(s + x)->v;
+  if (len & 4) {
+    reinterpret_cast<FlU32*>(d + x)->v = reinterpret_cast<const FlU32*>(s + x)->v;
+    x += 4;
+  }
+  if (len & 2) {
+    reinterpret_cast<FlU16*>(d + x)->v = reinterpret_cast<const FlU16*>(s + x)->v;
+    x += 2;
+  }
+  if (len & 1) d[x] = s[x];
+}
+
+}  // namespace
+
+// One bit per list word the table holds: idx[q] is the word's table index
+// (MOX_LOOKUP_NONE: absent; duplicates of a list word carry the same index).
+// *found += the bits this launch set.
+extern "C" __global__ __launch_bounds__(FL_T) void k_fl_mark(const uint64_t* idx, uint64_t nq, uint32_t* listed, uint64_t n,
+                                                             unsigned long long* found) {
+  __shared__ uint32_t s_nf;
+  if (threadIdx.x == 0) s_nf = 0;
+  __syncthreads();
+  uint32_t nf = 0;
+  for (uint64_t q = (uint64_t)blockIdx.x * FL_T + threadIdx.x; q < nq; q += (uint64_t)gridDim.x * FL_T) {
+    const uint64_t i = idx[q];
+    if (i < n) {  // (MOX_LOOKUP_NONE is no row)
+      const uint32_t bit = 1u << (i & 31);
+      nf += (atomicOr(listed + (i >> 5), bit) & bit) ? 0u : 1u;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o);
+  if ((threadIdx.x & 63) == 0 && nf) atomicAdd(&s_nf, nf);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_nf) atomicAdd(found, (unsigned long long)s_nf);
+}
+
+// keep[tile * FL_STEPS + step] = the ballot of "row is kept" over rows
+// tile * FL_TILE + step * 64 + lane; tc[0 * nt + tile] = kept rows, tc[1 * nt +
+// tile] = kept bytes, tc[2 * nt + tile] = kept count sum of the tile.
+extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(FlTab T, FlPred P, uint64_t* __restrict__ keep, uint64_t* __restrict__ tc) {
+  __shared__ uint64_t s_w[FL_WAVES][3];
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  for (uint64_t tile = blockIdx.x; tile < T.nt; tile += gridDim.x) {
+    const uint64_t base = tile * FL_TILE;
+    uint64_t nk = 0, nb = 0, cs = 0;
+#pragma unroll
+    for (int j = 0; j < FL_PER; j++) {
+      const uint64_t i = base + (uint32_t)j * FL_T + t;
+      bool k = false;
+      uint64_t len = 0, c = 0;
+      if (i < T.n) {
+        const uint64_t o = T.offs[i];
+        len = T.offs[i + 1] - o;
+        c = T.counts[i];
+        k = c >= P.min_count && c <= P.max_count && len >= P.min_len && len <= P.max_len;
+        if (k && P.list_mode) {
+          const bool in = (P.listed[i >> 5] >> (i & 31)) & 1u;
+          k = P.list_mode == 2 ? in : !in;
+        }
+        if (k && P.plen) {
+          k = len >= P.plen;  // a word shorter than the prefix is dropped
+          if (k) {
+            const FlKey16 w = *reinterpret_cast<const FlKey16*>(T.bytes + o);
+            k = (w.lo & P.m0) == P.p0 && (w.hi & P.m1) == P.p1;
+          }
+        }
+      }
+      const uint64_t m = __ballot(k);
+      if (lane == 0) keep[tile * FL_STEPS + (uint32_t)j * FL_WAVES + wv] = m;
+      if (k) {
+        nk++;
+        nb += len;
+        cs += c;
+      }
+    }
+    nk = fl_wave_sum64(nk);
+    nb = fl_wave_sum64(nb);
+    cs = fl_wave_sum64(cs);
+    if (lane == 0) {
+      s_w[wv][0] = nk;
+      s_w[wv][1] = nb;
+      s_w[wv][2] = cs;
+    }
+    __syncthreads();
+    if (t < 3) {
+      uint64_t v = 0;
+      for (int k = 0; k < FL_WAVES; k++) v += s_w[k][t];
+      tc[(uint64_t)t * T.nt + tile] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// Exclusive scans in place of the three tile arrays; the totals at tc[3 nt +
+// k], k = kept rows, kept bytes, kept count sum.  One workgroup with a running
+// carry (k_ac_scan's shape); a step takes FL_SCAN_STEP tiles of all three
+// arrays, FL_SCAN_PER consecutive ones per thread, behind one pair of barriers
+// (one array after the other, 1,024 tiles per step, took 440 us for the 89,159
+// tiles of a 91 M-word table: 264 dependent steps).
+extern "C" __global__ __launch_bounds__(1024) void k_fl_scan(uint64_t* tc, uint64_t nt) {
+  __shared__ uint64_t ws[3][16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint64_t carry0 = 0, carry1 = 0, carry2 = 0;
+  for (uint64_t c = 0; c < nt; c += FL_SCAN_STEP) {
+    const uint64_t i0 = c + (uint64_t)FL_SCAN_PER * threadIdx.x;
+    uint64_t sum[3], inc[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      uint64_t s = 0;
+#pragma unroll
+      for (int j = 0; j < FL_SCAN_PER; j++)
+        if (i0 + j < nt) s += tc[(uint64_t)k * nt + i0 + j];
+      sum[k] = s;
+      inc[k] = fl_wave_incscan64(s);
+      if (lane == 63) ws[k][wv] = inc[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      uint64_t pre = 0, tot = 0;
+      for (int j = 0; j < 16; j++) {
+        if (j < wv) pre += ws[k][j];
+        tot += ws[k][j];
+      }
+      // the thread's run again (its own values, not yet overwritten), now as running sums
+      uint64_t run = (k == 0 ? carry0 : k == 1 ? carry1 : carry2) + pre + inc[k] - sum[k];
+#pragma unroll
+      for (int j = 0; j < FL_SCAN_PER; j++)
+        if (i0 + j < nt) {
+          uint64_t* a = tc + (uint64_t)k * nt + i0 + j;
+          const uint64_t v = *a;
+          *a = run;
+          run += v;
+        }
+      if (k == 0) carry0 += tot;
+      else if (k == 1) carry1 += tot;
+      else carry2 += tot;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    tc[3 * nt + 0] = carry0;
+    tc[3 * nt + 1] = carry1;
+    tc[3 * nt + 2] = carry2;
+  }
+}
+
+// Every kept row at its scanned position (keep: k_fl_count's masks, tc:
+// k_fl_scan's output).
+extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint64_t* __restrict__ keep, const uint64_t* __restrict__ tc,
+                                                             FlOut out) {
+  __shared__ uint64_t s_w[FL_WAVES][2];   // a round's kept rows and kept bytes per wave
+  __shared__ uint64_t s_big_b[FL_TILE];   // words over FL_LANE_MAX bytes: byte offset in the output,
+  __shared__ uint16_t s_big_k[FL_TILE];   // ... row inside the tile
+  __shared__ uint32_t s_nbig;
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (blockIdx.x == 0 && t == 0) out.offs[out.kept] = out.bytes_kept;
+  for (uint64_t tile = blockIdx.x; tile < T.nt; tile += gridDim.x) {
+    const uint64_t base = tile * FL_TILE;
+    uint64_t rk = tc[tile], rb = tc[T.nt + tile];  // running output row and byte offset
+    // a tile that keeps nothing: the next tile's base is this one's (the same for every thread: no barrier is left out by some)
+    if ((tile + 1 < T.nt ? tc[tile + 1] : out.kept) == rk) continue;
+    if (t == 0) s_nbig = 0;
+    for (int j = 0; j < FL_PER; j++) {
+      const uint64_t i = base + (uint32_t)j * FL_T + t;
+      const uint64_t m = keep[tile * FL_STEPS + (uint32_t)j * FL_WAVES + wv];  // (no bit of a row past the table is set)
+      const bool k = (m >> lane) & 1ull;
+      uint64_t o = 0, len = 0, cnt = 0;
+      if (k) {
+        o = __builtin_nontemporal_load(T.offs + i);
+        len = __builtin_nontemporal_load(T.offs + i + 1) - o;
+        cnt = __builtin_nontemporal_load(T.counts + i);
+      }
+      const uint64_t inc = fl_wave_incscan64(len);
+      __syncthreads();  // the previous round's s_w has been read (and s_nbig is zero)
+      if (lane == 63) {
+        s_w[wv][0] = (uint64_t)__popcll(m);
+        s_w[wv][1] = inc;
+      }
+      __syncthreads();
+      uint64_t pk = rk, pb = rb;
+      for (uint32_t w = 0; w < (uint32_t)FL_WAVES; w++) {
+        if (w < wv) {
+          pk += s_w[w][0];
+          pb += s_w[w][1];
+        }
+        rk += s_w[w][0];
+        rb += s_w[w][1];
+      }
+      if (k) {
+        const uint64_t below = lane ? ~0ull >> (64 - lane) : 0ull;
+        const uint64_t r = pk + __popcll(m & below), bo = pb + inc - len;
+        if (r < out.kept && bo + len <= out.bytes_kept) {  // (always, for the masks the scan saw)
+          out.counts[r] = cnt;
+          out.offs[r] = bo;
+          if (len <= FL_LANE_MAX) {
+            fl_copy_lane(out.bytes + bo, T.bytes + o, len);
+          } else {  // a whole wave below
+            const uint32_t x = atomicAdd(&s_nbig, 1u);
+            s_big_b[x] = bo;
+            s_big_k[x] = (uint16_t)((uint32_t)j * FL_T + t);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // words over FL_LANE_MAX bytes: one wave each, 64 consecutive 8-byte words per step, then the tail bytes
+    const uint32_t nbig = s_nbig;
+    for (uint32_t x = wv; x < nbig; x += FL_WAVES) {
+      const uint64_t i = base + s_big_k[x];
+      const uint64_t o = T.offs[i], len = T.offs[i + 1] - o;
+      const uint8_t* s = T.bytes + o;
+      uint8_t* d = out.bytes + s_big_b[x];
+      const uint64_t nw = len / 8;
+      for (uint64_t wi = lane; wi < nw; wi += 64)
+        reinterpret_cast<FlU64*>(d + 8 * wi)->v = reinterpret_cast<const FlU64*>(s + 8 * wi)->v;
+      if (lane < (len & 7)) d[8 * nw + lane] = s[8 * nw + lane];
+    }
+    __syncthreads();  // the LDS arrays are the next tile's
+  }
+}
+
+namespace mox_host {
+
+void filter_free(mox_engine* e) {
+  for (DevBuf* b : {&e->f_tab[0][0], &e->f_tab[0][1], &e->f_tab[0][2], &e->f_tab[1][0], &e->f_tab[1][1], &e->f_tab[1][2], &e->f_tmp}) {
+    dfree(b->p);
+    *b = DevBuf{};
+  }
+  if (e->h_ftot) (void)hipHostFree(e->h_ftot);
+  e->h_ftot = nullptr;
+}
+
+}  // namespace mox_host
+
+extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_info* info) {
+  if (!e) return fail(MOX_EINVAL, "engine is NULL");
+  if (!f) return fail(MOX_EINVAL, "filter is NULL");
+  for (uint64_t r : f->reserved)
+    if (r) return fail(MOX_EINVAL, "filter: a reserved word is not 0");
+  if (f->flags & ~MOX_FILTER_COUNT_ONLY) return fail(MOX_EINVAL, "filter: unknown flags 0x%x", f->flags);
+  if (f->words_mode != MOX_FILTER_WORDS_DROP && f->words_mode != MOX_FILTER_WORDS_KEEP)
+    return fail(MOX_EINVAL, "filter: unknown words_mode %u", f->words_mode);
+  if (f->prefix_len > MOX_FILTER_PREFIX_MAX)
+    return fail(MOX_EINVAL, "filter: a prefix of %llu bytes (at most MOX_FILTER_PREFIX_MAX = %d)", (unsigned long long)f->prefix_len,
+                MOX_FILTER_PREFIX_MAX);
+  if (f->prefix_len && !f->prefix) return fail(MOX_EINVAL, "filter: NULL prefix");
+  const uint64_t nq = f->n_words;
+  if (nq > MOX_LOOKUP_MAX) return fail(MOX_EINVAL, "filter: %llu list words (at most MOX_LOOKUP_MAX = %u)", (unsigned long long)nq, MOX_LOOKUP_MAX);
+  if (nq && !f->word_offs) return fail(MOX_EINVAL, "filter: NULL word_offs");
+  for (uint64_t i = 0; i < nq; i++)
+    if (f->word_offs[i + 1] < f->word_offs[i]) return fail(MOX_EINVAL, "filter: list offsets decrease at word %llu", (unsigned long long)i);
+  if (nq && f->word_offs[nq] != f->word_offs[0] && !f->words) return fail(MOX_EINVAL, "filter: NULL words");
+  if (int rc = drain_async(e)) return rc;
+  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(e->device));
+  const mox_engine::Res r = e->res;
+  hipStream_t st = e->stream;
+  const Seq q = seq_of(e);
+  int rc;
+  // the list words' table indices, left in device memory by the lookup
+  const uint64_t* d_index = nullptr;
+  if (nq && (rc = lookup_device(e, f->words, f->word_offs, nq, nullptr, nullptr, nullptr, &d_index))) return rc;
+
+  FlPred P{};
+  P.min_count = f->min_count;
+  P.max_count = f->max_count ? f->max_count : ~0ull;
+  P.min_len = f->min_len;
+  P.max_len = f->max_len ? f->max_len : ~0ull;
+  P.plen = f->prefix_len;
+  if (P.plen) {
+    uint8_t pb[16] = {0};
+    memcpy(pb, f->prefix, P.plen);
+    memcpy(&P.p0, pb, 8);
+    memcpy(&P.p1, pb + 8, 8);
+    P.m0 = P.plen >= 8 ? ~0ull : (1ull << (8 * P.plen)) - 1ull;
+    P.m1 = P.plen <= 8 ? 0ull : P.plen >= 16 ? ~0ull : (1ull << (8 * (P.plen - 8))) - 1ull;
+  }
+  P.list_mode = f->words_mode == MOX_FILTER_WORDS_KEEP ? 2u : nq ? 1u : 0u;
+
+  // scratch: [tile arrays 3 nt | totals 3 | list_found | pad 4] [keep masks 16 nt] [list bitmap]
+  const FlTab T{r.counts, r.offs, r.bytes, r.n, (r.n + FL_TILE - 1) / FL_TILE};
+  const size_t tc_b = (3 * T.nt + 8) * 8, keep_b = T.nt * FL_STEPS * 8, bm_b = P.list_mode ? ((r.n + 63) / 64) * 8 + 8 : 0;
+  if ((rc = grow_dev(e->f_tmp, tc_b + keep_b + bm_b))) return rc;
+  if (!e->h_ftot) HIPCHK(hipHostMalloc((void**)&e->h_ftot, 64, hipHostMallocDefault));
+  uint64_t* tc = (uint64_t*)e->f_tmp.p;
+  uint64_t* keep = (uint64_t*)((uint8_t*)e->f_tmp.p + tc_b);
+  uint32_t* listed = (uint32_t*)((uint8_t*)e->f_tmp.p + tc_b + keep_b);
+  P.listed = listed;
+  uint64_t* tot = e->h_ftot;  // kept rows, kept bytes, kept count sum, list words found
+  for (int k = 0; k < 4; k++) tot[k] = 0;
+  uint64_t cap = 8ull * (uint64_t)e->n_cu;
+  if (const char* g = getenv("MOX_FILTER_GRID"))
+    if (atoll(g) > 0) cap = std::min<uint64_t>(cap, (uint64_t)atoll(g));
+  const uint32_t grid = (uint32_t)std::min(T.nt, cap);
+  if (T.n) {
+    HIPCHK(hipMemsetAsync(tc + 3 * T.nt, 0, 64, st));
+    if (P.list_mode) HIPCHK(hipMemsetAsync(listed, 0, bm_b, st));
+    if (nq) {
+      hipLaunchKernelGGL(k_fl_mark, dim3((uint32_t)std::min<uint64_t>((nq + FL_T - 1) / FL_T, 8ull * (uint64_t)e->n_cu)), dim3(FL_T), 0, st,
+                         d_index, nq, listed, T.n, (unsigned long long*)(tc + 3 * T.nt + 3));
+      q.step("k_fl_mark");
+    }
+    hipLaunchKernelGGL(k_fl_count, dim3(grid), dim3(FL_T), 0, st, T, P, keep, tc);
+    q.step("k_fl_count");
+    hipLaunchKernelGGL(k_fl_scan, dim3(1), dim3(1024), 0, st, tc, T.nt);
+    q.step("k_fl_scan");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(tot, tc + 3 * T.nt, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  if (tot[0] > r.n || tot[1] > r.nb || tot[3] > nq)
+    return fail(MOX_EHIP, "filter: inconsistent totals (%llu of %llu rows, %llu of %llu bytes, %llu of %llu list words)",
+                (unsigned long long)tot[0], (unsigned long long)r.n, (unsigned long long)tot[1], (unsigned long long)r.nb,
+                (unsigned long long)tot[3], (unsigned long long)nq);
+  mox_filter_info fi{};
+  fi.words_in = r.n;
+  fi.words_kept = tot[0];
+  fi.tokens_in = r.tokens;
+  fi.tokens_kept = tot[2];
+  fi.bytes_kept = tot[1];
+  fi.list_found = tot[3];
+  auto finish = [&]() {
+    fi.device_bytes = e->f_tmp.cap;
+    for (auto& set : e->f_tab)
+      for (DevBuf& b : set) fi.device_bytes += b.cap;
+    fi.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = fi;
+    return MOX_OK;
+  };
+  if (f->flags & MOX_FILTER_COUNT_ONLY) return finish();
+  if (const char* x = getenv("MOX_TEST_FAIL_FILTER"))
+    if (atoi(x)) return fail(MOX_ENOMEM, "filter: injected failure before the output is written (MOX_TEST_FAIL_FILTER)");
+  // the set of output buffers the result does not live in
+  DevBuf* dst = e->f_tab[(e->f_tab[0][0].p && r.counts == (const uint64_t*)e->f_tab[0][0].p) ? 1 : 0];
+  if ((rc = grow_dev(dst[0], 8 * tot[0] + 64)) || (rc = grow_dev(dst[1], 8 * (tot[0] + 1) + 64)) || (rc = grow_dev(dst[2], tot[1] + 64))) return rc;
+  const FlOut out{(uint64_t*)dst[0].p, (uint64_t*)dst[1].p, (uint8_t*)dst[2].p, tot[0], tot[1]};
+  if (T.n) {
+    hipLaunchKernelGGL(k_fl_emit, dim3(grid), dim3(FL_T), 0, st, T, keep, tc, out);
+    q.step("k_fl_emit");
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(hipMemsetAsync(out.offs, 0, 8, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  // the kept words are the result: order, sorted and folded as the source had them
+  mox_engine::Res& res = e->res;
+  res.counts = out.counts;
+  res.offs = out.offs;
+  res.bytes = out.bytes;
+  res.n = tot[0];
+  res.nb = tot[1];
+  res.tokens = tot[2];
+  res.pass = false;
+  res.exchanged = false;
+  return finish();
+}

@@ -2,8 +2,8 @@
 // pass driver (mox_engine.hip), the multi-GPU exchange / gather / engine group
 // (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
-// the device-resident accumulator (mox_accum.hip) and the device lookup
-// (mox_lookup.hip).
+// the device-resident accumulator (mox_accum.hip), the device lookup
+// (mox_lookup.hip) and the device filter (mox_filter.hip).
 // Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -192,6 +192,11 @@ struct mox_engine {
   // device lookup (mox_lookup.hip): scratch (outputs, query words, their hash set),
   // the pinned block the offsets go up and the outputs come back through
   DevBuf l_tmp, l_pin;
+  // device filter (mox_filter.hip): two sets of output buffers (counts, offs,
+  // bytes; 64 bytes of slack each; a call writes the set the result does not
+  // live in), the scratch (tile arrays, keep masks, list bitmap) and the pinned totals
+  DevBuf f_tab[2][3], f_tmp;
+  uint64_t* h_ftot = nullptr;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -277,4 +282,8 @@ void text_free(mox_engine* e);
 void accum_free(mox_engine* e);
 // ---- mox_lookup.hip
 void lookup_free(mox_engine* e);
+int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint64_t* counts, uint64_t* index,
+                  mox_lookup_info* info, const uint64_t** d_index);
+// ---- mox_filter.hip
+void filter_free(mox_engine* e);
 }  // namespace mox_host

@@ -481,13 +481,15 @@ void lookup_free(mox_engine* e) {
   e->l_pin = DevBuf{};
 }
 
-}  // namespace mox_host
-
-extern "C" int mox_lookup_words(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint64_t* counts,
-                                uint64_t* index, mox_lookup_info* info) {
+// mox_lookup_words; with d_index (mox_filter.hip) counts may be NULL, and
+// *d_index is the index array in device memory (n entries in l_tmp, valid until
+// the next lookup; NULL for n == 0): then only the control block comes back.
+int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint64_t* counts, uint64_t* index,
+                  mox_lookup_info* info, const uint64_t** d_index) {
   if (!e) return fail(MOX_EINVAL, "engine is NULL");
+  if (d_index) *d_index = nullptr;
   if (n > MOX_LOOKUP_MAX) return fail(MOX_EINVAL, "lookup: %llu words (at most MOX_LOOKUP_MAX = %u)", (unsigned long long)n, MOX_LOOKUP_MAX);
-  if (n && (!offs || !counts)) return fail(MOX_EINVAL, "lookup: NULL argument");
+  if (n && (!offs || (!counts && !d_index))) return fail(MOX_EINVAL, "lookup: NULL argument");
   uint64_t nb = 0;
   for (uint64_t i = 0; i < n; i++)
     if (offs[i + 1] < offs[i]) return fail(MOX_EINVAL, "lookup: offsets decrease at word %llu", (unsigned long long)i);
@@ -552,18 +554,27 @@ extern "C" int mox_lookup_words(mox_engine* e, const uint8_t* bytes, const uint6
   HIPCHK(hipGetLastError());
   // the one copy back: the counts and the control block, and the indices when they are asked for
   uint8_t* h_out = (uint8_t*)e->l_pin.p;
-  HIPCHK(hipMemcpyAsync(h_out, S.o_counts, index ? out_b : 8 * n + sizeof(LkCtl), hipMemcpyDeviceToHost, st));
+  if (counts) HIPCHK(hipMemcpyAsync(h_out, S.o_counts, index ? out_b : 8 * n + sizeof(LkCtl), hipMemcpyDeviceToHost, st));
+  else HIPCHK(hipMemcpyAsync(h_out + 8 * n, S.ctl, sizeof(LkCtl), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   LkCtl h;
   memcpy(&h, h_out + 8 * n, sizeof h);
   if (h.err || h.distinct > n || h.found > n)
     return fail(MOX_EHIP, "lookup: inconsistent query set (error %llu, %llu distinct, %llu found of %llu)", h.err, h.distinct, h.found,
                 (unsigned long long)n);
-  memcpy(counts, h_out, 8 * n);
-  if (index) memcpy(index, h_out + 8 * n + sizeof(LkCtl), 8 * n);
+  if (counts) memcpy(counts, h_out, 8 * n);
+  if (counts && index) memcpy(index, h_out + 8 * n + sizeof(LkCtl), 8 * n);
+  if (d_index) *d_index = S.o_index;
   li.distinct = h.distinct;
   li.found = h.found;
   li.tag_mismatch = h.tag_mismatch;
   if (info) *info = li;
   return MOX_OK;
+}
+
+}  // namespace mox_host
+
+extern "C" int mox_lookup_words(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint64_t* counts,
+                                uint64_t* index, mox_lookup_info* info) {
+  return lookup_device(e, bytes, offs, n, counts, index, info, nullptr);
 }

@@ -37,6 +37,10 @@ UNIQUE_ID_BYTES = 128
 TOP_MAX = 4096  # MOX_TOP_MAX: the most words Engine.top_words selects
 LOOKUP_MAX = 1 << 20  # MOX_LOOKUP_MAX: the most words one Engine.lookup call takes
 LOOKUP_NONE = (1 << 64) - 1  # MOX_LOOKUP_NONE: the index of a word the result does not hold
+FILTER_PREFIX_MAX = 16  # MOX_FILTER_PREFIX_MAX: the longest prefix Engine.filter_result takes
+FILTER_WORDS_DROP = 0   # MOX_FILTER_WORDS_DROP: listed words are removed (stop list)
+FILTER_WORDS_KEEP = 1   # MOX_FILTER_WORDS_KEEP: only listed words survive (vocabulary)
+FILTER_COUNT_ONLY = 0x1  # MOX_FILTER_COUNT_ONLY: fill the info, leave the result as it is
 
 
 class MoxError(RuntimeError):
@@ -100,6 +104,39 @@ class LookupInfo(ctypes.Structure):
         ("distinct", ctypes.c_uint64),
         ("found", ctypes.c_uint64),
         ("tag_mismatch", ctypes.c_uint64),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class Filter(ctypes.Structure):
+    """mox_filter: the predicate of mox_filter_result."""
+    _fields_ = [
+        ("min_count", ctypes.c_uint64),
+        ("max_count", ctypes.c_uint64),
+        ("min_len", ctypes.c_uint64),
+        ("max_len", ctypes.c_uint64),
+        ("prefix", ctypes.c_void_p),
+        ("prefix_len", ctypes.c_uint64),
+        ("words", ctypes.c_void_p),
+        ("word_offs", ctypes.POINTER(ctypes.c_uint64)),
+        ("n_words", ctypes.c_uint64),
+        ("words_mode", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class FilterInfo(ctypes.Structure):
+    """mox_filter_info: words and tokens in and kept, kept bytes, list words found, device bytes, ms."""
+    _fields_ = [
+        ("words_in", ctypes.c_uint64),
+        ("words_kept", ctypes.c_uint64),
+        ("tokens_in", ctypes.c_uint64),
+        ("tokens_kept", ctypes.c_uint64),
+        ("bytes_kept", ctypes.c_uint64),
+        ("list_found", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
         ("reserved", ctypes.c_uint64 * 4),
     ]
 
@@ -208,6 +245,7 @@ def lib(path=None):
             "mox_accumulate_reset": ([VP], I),
             "mox_accumulate_info": ([VP, P(AccumInfo)], I),
             "mox_lookup_words": ([VP, VP, P(U64), U64, P(U64), P(U64), P(LookupInfo)], I),
+            "mox_filter_result": ([VP, P(Filter), P(FilterInfo)], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -487,6 +525,63 @@ class Engine:
         if with_info:
             out += ({k: int(getattr(info, k)) for k in ("queries", "distinct", "found", "tag_mismatch")},)
         return out if len(out) > 1 else counts
+
+    # -- the result made smaller on the device (mox_filter_result)
+    def filter_result(self, min_count=0, max_count=None, min_len=0, max_len=None, prefix=b"", drop=None, keep=None,
+                      count_only=False):
+        """Keep the words of the device-resident result that satisfy every given
+        term; they become the engine's result, in the order they had, and tokens
+        the sum of their counts (mox_filter_result).  min_count <= count <=
+        max_count and min_len <= byte length <= max_len (None: no upper bound);
+        ``prefix``: the word's first bytes (at most FILTER_PREFIX_MAX); ``drop``: a
+        list of words to remove (a stop list), ``keep``: the only words to let
+        through (a vocabulary; [] keeps nothing) -- bytes, or str encoded as UTF-8,
+        taken verbatim, at most LOOKUP_MAX, and mutually exclusive.  count_only:
+        nothing changes, only the info is produced.  Returns the info dict
+        {"words_in", "words_kept", "tokens_in", "tokens_kept", "bytes_kept",
+        "list_found", "device_bytes", "ms"}."""
+        from . import spill
+
+        if drop is not None and keep is not None:
+            raise ValueError("drop and keep are mutually exclusive")
+        words = keep if keep is not None else drop
+        data = offs = None
+        if words is not None:
+            ws = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words]
+            data, offs, _ = spill.pack_pairs(ws, [])
+        return self.filter_result_packed(data, offs, keep is not None, min_count, max_count, min_len, max_len, prefix, count_only)
+
+    def filter_result_packed(self, data=None, offs=None, keep=False, min_count=0, max_count=None, min_len=0, max_len=None,
+                             prefix=b"", count_only=False):
+        """filter_result() with the word list already packed: word i is
+        data[offs[i]:offs[i+1]] (data: bytes or a numpy uint8 array, offs:
+        uint64[n + 1]; None: no list).  ``keep``: the list is a vocabulary, not a
+        stop list."""
+        import numpy as np
+
+        f = Filter()
+        f.min_count, f.max_count = min_count, max_count or 0  # (None, like the C struct's 0: no upper bound)
+        f.min_len, f.max_len = min_len, max_len or 0
+        pre = prefix.encode("utf-8") if isinstance(prefix, str) else bytes(prefix)
+        pbuf = ctypes.create_string_buffer(pre, max(1, len(pre)))
+        f.prefix, f.prefix_len = (ctypes.addressof(pbuf) if pre else None), len(pre)
+        f.words_mode = FILTER_WORDS_KEEP if keep else FILTER_WORDS_DROP
+        f.flags = FILTER_COUNT_ONLY if count_only else 0
+        if offs is not None:
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+            n = offs.size - 1
+            if n < 0:
+                raise ValueError("offs needs n + 1 entries")
+            buf = data if isinstance(data, np.ndarray) else np.frombuffer(data or b"", dtype=np.uint8)
+            buf = np.ascontiguousarray(buf, dtype=np.uint8)
+            if n and int(offs[-1]) > buf.size:
+                raise ValueError("offsets run past the words' bytes")
+            f.words = buf.ctypes.data if buf.size else None
+            f.word_offs = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+            f.n_words = n
+        info = FilterInfo()
+        self._c(self._L.mox_filter_result(self._h, ctypes.byref(f), ctypes.byref(info)))
+        return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
 
     def stats(self):
         s = Stats()
