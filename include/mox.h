@@ -226,7 +226,8 @@ int mox_run_shards(mox_engine* e, const mox_shard* shards);
  * shard (mox_device_alloc / mox_memcpy_h2d). */
 int mox_group_size(const mox_engine* e);
 mox_engine* mox_group_member(mox_engine* e, int i);
-/* Copy the table of the last run (or of the last exchange) to the host. */
+/* Copy the table of the last run (or of the last exchange) to the host.
+ * (A row range of it: mox_fetch_rows, below.) */
 int mox_fetch_table(mox_engine* e, mox_table** out);
 /* Reorder the device-resident result table bytewise ascending (Rust String
  * Ord) on the GPU, without fetching it (e.g. the root's table after
@@ -252,7 +253,9 @@ int mox_sort_result(mox_engine* e);
  * calls with another k, mox_fetch_table, an exchange all see it unchanged).
  * k == 0 or an empty result: an empty table.  MOX_EINVAL: k > MOX_TOP_MAX or a
  * NULL argument; MOX_ESTATE: no run yet.  An engine group: member 0's gathered
- * result. */
+ * result.  Once the result is ranked (mox_rank_result), table order is count
+ * order: the words this call selects are the ranked table's first rows, and
+ * mox_fetch_rows reaches past MOX_TOP_MAX. */
 #define MOX_TOP_MAX 4096
 int mox_top_words(mox_engine* e, size_t k, mox_table** out);
 /* The device-resident result as final_result.txt text, formatted on the GPU:
@@ -276,7 +279,9 @@ int mox_top_words(mox_engine* e, size_t k, mox_table** out);
  * mox_top_words, exchange or a second rendering sees the same table).  A count
  * of 0 (mox_reduce_pairs lets one through) renders as "0".  MOX_ESTATE: no run
  * yet; MOX_EINVAL: a NULL argument; MOX_EIO: the file cannot be opened or
- * written.  An engine group: member 0's gathered result. */
+ * written.  An engine group: member 0's gathered result.  A ranked result
+ * (mox_rank_result) is rendered in count order and is not re-sorted,
+ * MOX_F_SORT_BYTES or not: an explicit ranking wins over the flag. */
 int mox_write_result(mox_engine* e, const char* path);
 int mox_result_text(mox_engine* e, uint8_t** text, uint64_t* len);
 void mox_text_free(uint8_t* text);
@@ -461,6 +466,85 @@ typedef struct mox_filter_info {
   uint64_t reserved[4];
 } mox_filter_info;
 int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_info* info /* may be NULL */);
+
+/* ---- ranking the device-resident result by count, fetching it by rows ---- */
+/* Reorders the device-resident result by count, on the GPU: the same words
+ * and counts, most frequent first, or least frequent first with
+ * MOX_RANK_ASCENDING.  Nothing is fetched and no host pass runs over the
+ * table.  Afterwards mox_fetch_table / mox_fetch_rows, mox_write_result /
+ * mox_result_text, mox_top_words, mox_lookup_words (its indices are ranks),
+ * mox_filter_result and mox_accumulate work on the ranked table as on any
+ * result: "the first N rows by count", "page k of the ranked vocabulary" and
+ * "final_result.txt sorted by count" need no full fetch.
+ * Order: count descending (ascending with the flag); words with equal counts
+ * keep the order they had in device memory at the call -- the sort is stable.
+ * This is the tie rule of mox_top_words and mox_print_top_words, so
+ * mox_top_words(k) taken before the call equals the first min(k, n) rows
+ * after it, and mox_sort_result followed by mox_rank_result gives the
+ * deterministic order "count descending, then bytewise" (engine order can
+ * differ from run to run among words longer than 16 bytes).  Counts are
+ * compared as full u64: 0 and 2^64 - 1 (mox_reduce_pairs lets both through)
+ * sort like any other.  Ties keep table order in both directions, so the
+ * ascending ranking is the descending one reversed only where counts are
+ * distinct.
+ * Works on every form of result: a run's, mox_reduce_pairs, exchanged,
+ * gathered, mox_run_shards, sorted, filtered, the accumulator's total, a
+ * ranked one (ranking twice, or ascending after descending, is legal).
+ * Completes pending asynchronous passes first.  An engine group: member 0's
+ * gathered result, on member 0.
+ * State: tokens, the number of words, the byte total, the folded state and
+ * the accumulator are unchanged.  As after a filter, the new result is no
+ * pass's table and no exchanged one: mox_exchange / mox_gather afterwards
+ * return MOX_ESTATE, so distributed callers gather first and rank at the
+ * root.  The result is marked ranked and no longer counts as bytewise sorted
+ * (unless it has at most one word): a ranked result is NOT re-sorted by the
+ * implicit MOX_F_SORT_BYTES sort of mox_fetch_table, mox_fetch_rows,
+ * mox_write_result and mox_result_text -- an explicit ranking wins over the
+ * flag.  An explicit mox_sort_result sorts it bytewise and ends the ranking,
+ * as does whatever replaces the result (a run, mox_reduce_pairs, an exchange,
+ * a gather, an accumulate merge).  mox_filter_result keeps it (a subset of a
+ * ranked table is ranked), and so does the first mox_accumulate into an empty
+ * accumulator (the result stays the table it was).
+ * info may be NULL.  digit_passes: only the bytes of the largest count are
+ * sorted, ceil(bitlen(max_count) / 8) radix passes of 8 bits; max_count == 0
+ * runs none (the order stays).  Empty and one-word tables succeed and launch
+ * nothing that reads rows.  Device memory: two sets of output buffers (a call
+ * writes the set the result does not live in) and 24 bytes of scratch per
+ * word plus 1 KiB per 4096 words, held by the engine until mox_engine_destroy.
+ * MOX_ESTATE: no result yet.  MOX_EINVAL: a NULL engine, unknown flag bits, or
+ * a table of more than MOX_RANK_MAX_WORDS words (row indices travel as u32).
+ * MOX_ENOMEM: the scratch or the output buffers cannot be allocated.  After
+ * any error the result is exactly what it was and *info is untouched.
+ * MOX_RANK_GRID=<workgroups> (tests; read at each call) caps the grid of every
+ * pass over rows; MOX_TEST_FAIL_RANK=1 (tests; read at each call) returns
+ * MOX_ENOMEM after the permutation is computed and before any output buffer is
+ * written. */
+#define MOX_RANK_ASCENDING 0x1u   /* least frequent first; default: most frequent first */
+#define MOX_RANK_MAX_WORDS 0xFFFFFFFFull
+typedef struct mox_rank_info {
+  uint64_t words, tokens;      /* of the result (unchanged by the call) */
+  uint64_t max_count;          /* largest count in the table (0 for an empty one) */
+  uint64_t digit_passes;       /* radix passes that ran */
+  uint64_t device_bytes;       /* device memory the ranking holds after the call */
+  double ms;                   /* wall time of the call */
+  uint64_t reserved[4];
+} mox_rank_info;
+int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* info /* may be NULL */);
+/* Rows [first, min(first + n, N)) of the device-resident result (N words) as
+ * a normal mox_table (mox_table_free), offs rebased to 0; tokens is the whole
+ * result's total, as mox_top_words reports it.  The rows are taken in the
+ * order mox_fetch_table would return them: the same implicit MOX_F_SORT_BYTES
+ * sort runs first (flag set, result neither sorted nor ranked), so pages laid
+ * end to end are byte for byte the fetched table.  Only the slice crosses
+ * PCIe: its offsets first, then its counts and exactly its bytes; nothing
+ * sized by the whole table is copied (one exception: where the implicit sort
+ * finds no room for its device scratch the order exists only on the host, so
+ * the whole table is fetched and sorted there, as mox_fetch_table does, for
+ * every page).  first >= N or n == 0: an empty table.  The result stays where
+ * it is.  Completes pending asynchronous passes first.  MOX_ESTATE: no result
+ * yet; MOX_EINVAL: a NULL argument.  An engine group: member 0's gathered
+ * result. */
+int mox_fetch_rows(mox_engine* e, uint64_t first, uint64_t n, mox_table** out);
 
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 

@@ -22,6 +22,11 @@
 // --word: words seen fewer than N times and the words of FILE go.  FILE holds
 // words split at ASCII whitespace, taken verbatim (lowercase them: the table's
 // words are).  Without these options the output is what it always was.
+// --by-count orders the device-resident result by count, most frequent first,
+// words with equal counts bytewise (mox_sort_result, then the stable
+// mox_rank_result), after any filter and before the file is written:
+// final_result.txt is then the same from run to run.  Without the option
+// every output is what it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
@@ -41,7 +46,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> words;
   unsigned long long min_count = 0;
   std::string stop_path;
-  bool have_stop = false;
+  bool have_stop = false, by_count = false;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
@@ -49,6 +54,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--word") && i + 1 < argc) words.push_back(argv[++i]);
     else if (!strcmp(argv[i], "--min-count") && i + 1 < argc) min_count = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--stop") && i + 1 < argc) { stop_path = argv[++i]; have_stop = true; }
+    else if (!strcmp(argv[i], "--by-count")) by_count = true;
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) paths.push_back("shakes.txt");
@@ -93,6 +99,8 @@ int main(int argc, char** argv) {
     f.words_mode = MOX_FILTER_WORDS_DROP;
     rc = mox_filter_result(e, &f, nullptr);
   }
+  if (rc == MOX_OK && by_count) rc = mox_sort_result(e);
+  if (rc == MOX_OK && by_count) rc = mox_rank_result(e, 0, nullptr);
   if (rc == MOX_OK) rc = mox_write_result(e, out.c_str());
   if (rc == MOX_OK) rc = mox_top_words(e, 10, &t);
   if (rc == MOX_OK) rc = mox_print_top_words(t, 10);

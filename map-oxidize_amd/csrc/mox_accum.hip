@@ -353,6 +353,7 @@ void acc_as_result(mox_engine* e) {
   r.pass = false;
   r.exchanged = false;
   r.sorted = e->acc.sorted;
+  r.ranked = e->acc.ranked;
   r.folded = true;
   e->have_result = true;
 }
@@ -386,6 +387,7 @@ void acc_commit(mox_engine* e, uint64_t passes) {
   e->acc.nb = e->res.nb;
   e->acc.tokens = e->res.tokens;
   e->acc.sorted = e->res.sorted;
+  e->acc.ranked = e->res.ranked;
   e->acc.passes = passes;
   e->res.folded = true;
 }

@@ -960,6 +960,7 @@ int bsort_once(mox_engine* e, bool checked) {
   r.offs = oo;
   r.bytes = (const uint8_t*)e->s_bytes.p;
   r.sorted = true;
+  r.ranked = false;
   return MOX_OK;
 }
 

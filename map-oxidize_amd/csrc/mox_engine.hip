@@ -10,6 +10,8 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <memory>
+
 #include "mox_host.h"
 #include "mox_unicode_tables.h"
 
@@ -446,6 +448,7 @@ void set_result(mox_engine* e, const Ctl& h) {
   e->res.pass = true;
   e->res.exchanged = false;
   e->res.sorted = false;
+  e->res.ranked = false;
   e->res.folded = false;
   e->have_result = true;
 }
@@ -1045,6 +1048,7 @@ void mox_engine_destroy(mox_engine* e) {
   accum_free(e);
   lookup_free(e);
   filter_free(e);
+  rank_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {
@@ -1161,22 +1165,30 @@ int mox_run_range(mox_engine* e, const void* d_buf, size_t buf_len, size_t own_b
 
 int mox_run_device(mox_engine* e, const void* d_text, size_t len) { return mox_run_range(e, d_text, len, 0, len, 1); }
 
+// MOX_F_SORT_BYTES before a fetch: bytewise order on the GPU (mox_bsort.hip),
+// unless the result is sorted already or was ranked (an explicit ranking wins
+// over the flag).  *host_sort: the table is too big for the sort's device
+// scratch, so the fetched copy is to be sorted on the host.
+static int sort_for_fetch(mox_engine* e, bool* host_sort) {
+  *host_sort = false;
+  if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted && !e->res.ranked) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = bsort_table(e);
+    if (rc == MOX_ENOMEM) *host_sort = true;
+    else if (rc) return rc;
+    e->stats.ms_sort = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return MOX_OK;
+}
+
 int mox_fetch_table(mox_engine* e, mox_table** out) {
   if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
   *out = nullptr;
   if (int rc = drain_async(e)) return rc;
   if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
   HIPCHK(hipSetDevice(e->device));
-  // MOX_F_SORT_BYTES: bytewise order on the GPU (mox_bsort.hip) before the copy;
-  // a table too big for the sort's device scratch is sorted on the host below
   bool host_sort = false;
-  if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = bsort_table(e);
-    if (rc == MOX_ENOMEM) host_sort = true;
-    else if (rc) return rc;
-    e->stats.ms_sort = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
+  if (int rc = sort_for_fetch(e, &host_sort)) return rc;
   const bool timing = (e->flags & MOX_F_TIMING) != 0;
   if (timing) HIPCHK(hipEventRecord(e->ev[6], e->stream));
   const mox_engine::Res& r = e->res;
@@ -1217,11 +1229,91 @@ int mox_sort_result(mox_engine* e) {
   if (!e) return fail(MOX_EINVAL, "NULL argument");
   if (int rc = drain_async(e)) return rc;
   if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
-  if (e->res.sorted) return MOX_OK;
+  if (e->res.sorted) {  // (sorted and ranked at once: a table of at most one word)
+    e->res.ranked = false;
+    return MOX_OK;
+  }
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = bsort_table(e);
   e->stats.ms_sort = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (!rc) e->res.ranked = false;  // (bsort_table leaves a table of at most one word as it is)
   return rc;
+}
+
+// A mox_table of cnt rows and nbytes word bytes in one block (mox_table_free),
+// offs[0] = 0 and the rest for the caller to fill; NULL: no memory.
+static mox_table* table_of_rows(uint64_t cnt, uint64_t nbytes, uint64_t tokens) {
+  const size_t bytes = sizeof(mox_table) + (cnt + 1) * 8 * 2 + nbytes + 16;
+  uint8_t* mem = (uint8_t*)malloc(bytes);
+  if (!mem) return nullptr;
+  mox_table* t = (mox_table*)mem;
+  uint64_t* counts = (uint64_t*)(mem + sizeof(mox_table));
+  uint64_t* offs = counts + cnt + 1;
+  t->n = cnt;
+  t->tokens = tokens;
+  t->counts = counts;
+  t->offs = offs;
+  t->bytes = (uint8_t*)(offs + cnt + 1);
+  offs[0] = 0;
+  return t;
+}
+
+int mox_fetch_rows(mox_engine* e, uint64_t first, uint64_t n, mox_table** out) {
+  if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (int rc = drain_async(e)) return rc;
+  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  HIPCHK(hipSetDevice(e->device));
+  bool host_sort = false;
+  if (int rc = sort_for_fetch(e, &host_sort)) return rc;
+  const mox_engine::Res& r = e->res;
+  const uint64_t lo = std::min(first, r.n), cnt = std::min(n, r.n - lo);
+  if (host_sort) {
+    // the device sort's scratch does not fit: the order of the rows exists only
+    // in a host-sorted copy of the whole table (as mox_fetch_table makes it)
+    mox_table* whole = nullptr;
+    if (int rc = mox_fetch_table(e, &whole)) return rc;
+    const uint64_t b0 = whole->offs[lo], nbytes = whole->offs[lo + cnt] - b0;
+    mox_table* t = table_of_rows(cnt, nbytes, r.tokens);
+    if (t) {
+      for (uint64_t i = 0; i < cnt; i++) {
+        const_cast<uint64_t*>(t->counts)[i] = whole->counts[lo + i];
+        const_cast<uint64_t*>(t->offs)[i + 1] = whole->offs[lo + i + 1] - b0;
+      }
+      if (nbytes) memcpy(const_cast<uint8_t*>(t->bytes), whole->bytes + b0, nbytes);
+    }
+    mox_table_free(whole);
+    if (!t) return fail(MOX_ENOMEM, "host allocation of a table of %llu rows failed", (unsigned long long)cnt);
+    *out = t;
+    return MOX_OK;
+  }
+  // the offsets of the slice first: they say which bytes it has
+  const std::unique_ptr<uint64_t, void (*)(void*)> so_mem((uint64_t*)calloc(cnt + 1, 8), free);
+  uint64_t* so = so_mem.get();
+  if (!so) return fail(MOX_ENOMEM, "host allocation of %llu offsets failed", (unsigned long long)cnt + 1);
+  if (cnt) {
+    HIPCHK(hipMemcpyAsync(so, r.offs + lo, (cnt + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  const uint64_t b0 = so[0], b1 = so[cnt];
+  if (b1 < b0 || b1 > r.nb) return fail(MOX_EHIP, "fetch rows: offsets [%llu, %llu) of %llu table bytes", (unsigned long long)b0,
+                                        (unsigned long long)b1, (unsigned long long)r.nb);
+  mox_table* t = table_of_rows(cnt, b1 - b0, r.tokens);
+  if (!t) return fail(MOX_ENOMEM, "host allocation of a table of %llu rows failed", (unsigned long long)cnt);
+  for (uint64_t i = 0; i < cnt; i++) const_cast<uint64_t*>(t->offs)[i + 1] = so[i + 1] - b0;
+  hipError_t err = hipSuccess;
+  if (cnt) {
+    err = hipMemcpyAsync(const_cast<uint64_t*>(t->counts), r.counts + lo, cnt * 8, hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess && b1 > b0)
+      err = hipMemcpyAsync(const_cast<uint8_t*>(t->bytes), r.bytes + b0, b1 - b0, hipMemcpyDeviceToHost, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  }
+  if (err != hipSuccess) {
+    free(t);
+    return fail(MOX_EHIP, "fetch rows: copying the slice failed: %s", hipGetErrorString(err));
+  }
+  *out = t;
+  return MOX_OK;
 }
 
 void mox_table_free(mox_table* t) { free(t); }

@@ -3,7 +3,8 @@
 // (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
 // the device-resident accumulator (mox_accum.hip), the device lookup
-// (mox_lookup.hip) and the device filter (mox_filter.hip).
+// (mox_lookup.hip), the device filter (mox_filter.hip) and the device ranking
+// (mox_rank.hip).
 // Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -169,13 +170,14 @@ struct mox_engine {
     bool pass = false;       // true: the t_* buffers of the last pass (an exchange can start from it)
     bool exchanged = false;  // true: the final table of an exchange (this rank's words are final: gatherable)
     bool sorted = false;     // true: in bytewise order (bsort_table)
+    bool ranked = false;     // true: ordered by count (mox_rank_result): the implicit MOX_F_SORT_BYTES sort leaves it alone
     bool folded = false;     // true: already part of the accumulator (mox_accumulate takes a result once)
   } res;
   // mox_accumulate (mox_accum.hip): the running total as a saved table (a_tab:
   // counts, offs, bytes; 64 bytes of slack each), the packer's tile counts and
   // their pinned totals
   struct Acc {
-    bool have = false, sorted = false;
+    bool have = false, sorted = false, ranked = false;
     uint64_t n = 0, nb = 0, tokens = 0, passes = 0;
   } acc;
   DevBuf a_tab[3], a_tc;
@@ -197,6 +199,11 @@ struct mox_engine {
   // live in), the scratch (tile arrays, keep masks, list bitmap) and the pinned totals
   DevBuf f_tab[2][3], f_tmp;
   uint64_t* h_ftot = nullptr;
+  // device ranking (mox_rank.hip): two sets of output buffers (as f_tab), the
+  // scratch (keys, row indices, digit counts, tile bytes) and the pinned block
+  // maxima / totals
+  DevBuf r_tab[2][3], r_tmp;
+  uint64_t* h_rmax = nullptr;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -286,4 +293,6 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
                   mox_lookup_info* info, const uint64_t** d_index);
 // ---- mox_filter.hip
 void filter_free(mox_engine* e);
+// ---- mox_rank.hip
+void rank_free(mox_engine* e);
 }  // namespace mox_host

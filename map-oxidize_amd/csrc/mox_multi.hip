@@ -498,6 +498,7 @@ int gather_impl(mox_engine* e, int P, int me, int root, Transport& T) {
     e->res.pass = false;
     e->res.exchanged = false;  // gathered: final, not gathered again
     e->res.sorted = all_sorted && e->xp && e->xp->ranged;
+    e->res.ranked = false;
     e->res.folded = false;
   } else {
     HIPCHK(hipStreamSynchronize(s));  // the send buffer is reused by the next exchange
@@ -834,6 +835,7 @@ int group_gather(Group& G) {
   res.pass = false;
   res.exchanged = false;
   res.sorted = all_sorted;
+  res.ranked = false;
   res.folded = false;
   root->have_result = true;
   root->stats.gather_bytes = recv_bytes;

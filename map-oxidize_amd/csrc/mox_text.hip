@@ -394,7 +394,7 @@ int tx_prepare(mox_engine* e) {
   if (int rc = drain_async(e)) return rc;
   if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
   HIPCHK(hipSetDevice(e->device));
-  if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted) {
+  if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted && !e->res.ranked) {
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = bsort_table(e);
     e->stats.ms_sort = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

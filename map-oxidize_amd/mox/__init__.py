@@ -41,6 +41,8 @@ FILTER_PREFIX_MAX = 16  # MOX_FILTER_PREFIX_MAX: the longest prefix Engine.filte
 FILTER_WORDS_DROP = 0   # MOX_FILTER_WORDS_DROP: listed words are removed (stop list)
 FILTER_WORDS_KEEP = 1   # MOX_FILTER_WORDS_KEEP: only listed words survive (vocabulary)
 FILTER_COUNT_ONLY = 0x1  # MOX_FILTER_COUNT_ONLY: fill the info, leave the result as it is
+RANK_ASCENDING = 0x1  # MOX_RANK_ASCENDING: Engine.rank_result orders least frequent first
+RANK_MAX_WORDS = (1 << 32) - 1  # MOX_RANK_MAX_WORDS: the most words Engine.rank_result takes
 
 
 class MoxError(RuntimeError):
@@ -135,6 +137,19 @@ class FilterInfo(ctypes.Structure):
         ("tokens_kept", ctypes.c_uint64),
         ("bytes_kept", ctypes.c_uint64),
         ("list_found", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class RankInfo(ctypes.Structure):
+    """mox_rank_info: words and tokens of the result, its largest count, radix passes run, device bytes, ms."""
+    _fields_ = [
+        ("words", ctypes.c_uint64),
+        ("tokens", ctypes.c_uint64),
+        ("max_count", ctypes.c_uint64),
+        ("digit_passes", ctypes.c_uint64),
         ("device_bytes", ctypes.c_uint64),
         ("ms", ctypes.c_double),
         ("reserved", ctypes.c_uint64 * 4),
@@ -246,6 +261,8 @@ def lib(path=None):
             "mox_accumulate_info": ([VP, P(AccumInfo)], I),
             "mox_lookup_words": ([VP, VP, P(U64), U64, P(U64), P(U64), P(LookupInfo)], I),
             "mox_filter_result": ([VP, P(Filter), P(FilterInfo)], I),
+            "mox_rank_result": ([VP, ctypes.c_uint32, P(RankInfo)], I),
+            "mox_fetch_rows": ([VP, U64, U64, P(P(_Table))], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -582,6 +599,25 @@ class Engine:
         info = FilterInfo()
         self._c(self._L.mox_filter_result(self._h, ctypes.byref(f), ctypes.byref(info)))
         return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+
+    # -- the result ordered by count on the device (mox_rank_result), and read by rows
+    def rank_result(self, ascending=False):
+        """Reorder the device-resident result by count on the GPU, most frequent
+        first (``ascending``: least frequent first); words with equal counts keep
+        the order they had, so sort_result() first gives "count, then bytewise"
+        (mox_rank_result).  Returns the info dict {"words", "tokens", "max_count",
+        "digit_passes", "device_bytes", "ms"}."""
+        info = RankInfo()
+        self._c(self._L.mox_rank_result(self._h, RANK_ASCENDING if ascending else 0, ctypes.byref(info)))
+        return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+
+    def fetch_rows(self, first, n):
+        """Rows [first, first + n) of the device-resident result as a Table, in the
+        order fetch() returns them; only these rows are copied (mox_fetch_rows).
+        tokens is the whole result's."""
+        t = ctypes.POINTER(_Table)()
+        self._c(self._L.mox_fetch_rows(self._h, first, n, ctypes.byref(t)))
+        return Table(t, self._L)
 
     def stats(self):
         s = Stats()
