@@ -41,12 +41,11 @@
 //
 // Key loads: the 16 key bytes of a row at byte offset o come from three aligned
 // 8-byte loads at o & ~7 and a funnel shift, so they read up to 23 bytes past
-// o; a long word's copy reads whole 8-byte words the same way.  Every bytes
-// buffer a result can live in carries 64 bytes of slack past the table's bytes
-// (t_bytes: realloc_sized; g_bytes: gather_impl / group_gather; s_bytes:
-// bsort_table; a_bytes: acc_reserve below), and a row starts at o <= nb, so no
-// load leaves its allocation and none is clamped.  What is read past a word is
-// masked by the word's length before the NUL test, the hash and every store.
+// o; a long word's copy reads whole 8-byte words the same way (mox_dev.h:
+// funnel, word_at).  That is inside the slack of every bytes buffer a result
+// can live in (mox_dev.h: the slack contract), so no load leaves its
+// allocation and none is clamped.  What is read past a word is masked by the
+// word's length before the NUL test, the hash and every store.
 // A zero-length row (no result holds one) loads nothing: it becomes a header
 // with no bytes.
 //
@@ -58,6 +57,7 @@
 #include <cerrno>
 #include <cstdlib>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -86,13 +86,7 @@ struct AcOut {
 
 constexpr uint64_t AC_FNV0 = 0xcbf29ce484222325ull;
 __device__ __forceinline__ uint64_t ac_fnv_step(uint64_t h, uint64_t b) { return (h ^ b) * 0x100000001b3ull; }
-__device__ __forceinline__ uint64_t ac_mask(uint64_t x, uint64_t n) { return n >= 8 ? x : x & ((1ull << (8 * n)) - 1ull); }
 __device__ __forceinline__ uint64_t ac_haszero(uint64_t v) { return (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull; }
-// 8-byte word i of the bytes from offset o on (q = the aligned word that holds o, sh = 8 (o & 7))
-__device__ __forceinline__ uint64_t ac_word(const uint64_t* q, uint32_t sh, uint64_t i) {
-  const uint64_t a = q[i], b = q[i + 1];
-  return sh ? (a >> sh) | (b << (64 - sh)) : a;
-}
 
 // Row classification.  len in 1..16: the key, masked by the length, and
 // whether it is NUL-free (bytes past the length are filled with ones for the
@@ -102,26 +96,13 @@ __device__ __forceinline__ bool ac_short(const uint8_t* bytes, uint64_t o, uint6
   const uint64_t* q = reinterpret_cast<const uint64_t*>(bytes + (o & ~7ull));
   const uint32_t sh = (uint32_t)(o & 7u) * 8u;
   const uint64_t a = q[0], b = q[1], c = q[2];
-  k0 = sh ? (a >> sh) | (b << (64 - sh)) : a;
+  k0 = sh ? (a >> sh) | (b << (64 - sh)) : a;  // (funnel, written out: three loads in flight whatever the length)
   k1 = sh ? (b >> sh) | (c << (64 - sh)) : b;
-  k0 = ac_mask(k0, len);
-  k1 = len > 8 ? ac_mask(k1, len - 8) : 0ull;
+  k0 = mask_low(k0, len);
+  k1 = len > 8 ? mask_low(k1, len - 8) : 0ull;
   const uint64_t f0 = len >= 8 ? 0ull : ~0ull << (8 * len);
   const uint64_t f1 = len >= 16 ? 0ull : (len <= 8 ? ~0ull : ~0ull << (8 * (len - 8)));
   return !(ac_haszero(k0 | f0) | ac_haszero(k1 | f1));
-}
-
-__device__ __forceinline__ uint64_t ac_wave_sum64(uint64_t x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ __forceinline__ uint64_t ac_wave_incscan64(uint64_t x) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
 }
 
 }  // namespace
@@ -151,9 +132,9 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(AcTab a, AcTab b, 
         }
       }
     }
-    ns = ac_wave_sum64(ns);
-    nl = ac_wave_sum64(nl);
-    lb = ac_wave_sum64(lb);
+    ns = wave_sum(ns);
+    nl = wave_sum(nl);
+    lb = wave_sum(lb);
     if (lane == 0) {
       s_w[wv][0] = ns;
       s_w[wv][1] = nl;
@@ -172,34 +153,12 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(AcTab a, AcTab b, 
 // Exclusive scans in place of the three tile arrays, each in two segments
 // (source 0's tiles [0, nt0), source 1's [nt0, nt0 + nt1)); the totals at
 // tc[3 nt + 3 s + k], k = short rows, long rows, long bytes of source s.  One
-// workgroup, 1,024 values per step with a running carry (k_tx_scan's shape).
-// Also clears the word behind the totals, k_ac_pack's zero-count flag.
+// workgroup (mox_dev.h: scan_one_wg).  Also clears the word behind the totals,
+// k_ac_pack's zero-count flag.
 extern "C" __global__ __launch_bounds__(1024) void k_ac_scan(uint64_t* tc, uint64_t nt0, uint64_t nt1) {
-  __shared__ uint64_t ws[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint64_t nt = nt0 + nt1;
   for (int k = 0; k < 3; k++)
-    for (int s = 0; s < 2; s++) {
-      uint64_t* a = tc + (uint64_t)k * nt + (s ? nt0 : 0);
-      const uint64_t m = s ? nt1 : nt0;
-      uint64_t carry = 0;
-      for (uint64_t c = 0; c < m; c += 1024) {
-        const uint64_t i = c + threadIdx.x;
-        const uint64_t x = i < m ? a[i] : 0ull;
-        const uint64_t inc = ac_wave_incscan64(x);
-        if (lane == 63) ws[wv] = inc;
-        __syncthreads();
-        uint64_t pre = 0, tot = 0;
-        for (int j = 0; j < 16; j++) {
-          if (j < wv) pre += ws[j];
-          tot += ws[j];
-        }
-        if (i < m) a[i] = carry + pre + inc - x;
-        carry += tot;
-        __syncthreads();
-      }
-      if (threadIdx.x == 0) tc[3 * nt + 3 * s + k] = carry;
-    }
+    for (int s = 0; s < 2; s++) scan_one_wg<uint64_t, 1024>(tc + (uint64_t)k * nt + (s ? nt0 : 0), s ? nt1 : nt0, tc + 3 * nt + 3 * s + k);
   if (threadIdx.x == 0) tc[3 * nt + 6] = 0;  // k_ac_pack's flag: a short row with count 0
 }
 
@@ -239,7 +198,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
       if (__ballot(is_s && cnt == 0) && lane == 0) tc[3 * nt + 6] = 1;
       const uint64_t below = lane ? ~0ull >> (64 - lane) : 0ull;
       const uint64_t pl = is_l ? (len + 7) & ~7ull : 0ull;
-      const uint64_t inc = ac_wave_incscan64(pl);
+      const uint64_t inc = wave_incscan<uint64_t>(pl);
       __syncthreads();  // the previous round's s_w has been read (and s_nbig is zero)
       if (lane == 63) {
         s_w[wv][0] = (uint64_t)__popcll(ms);
@@ -269,7 +228,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
           uint64_t h = AC_FNV0;
           for (uint64_t x = 0; 8 * x < len; x++) {
             const uint64_t m = len - 8 * x;
-            const uint64_t v = ac_mask(ac_word(q, sh, x), m);
+            const uint64_t v = mask_low(word_at(q, sh, x), m);
             d[x] = v;
             const uint32_t nb = m < 8 ? (uint32_t)m : 8u;
             for (uint32_t y = 0; y < nb; y++) h = ac_fnv_step(h, (v >> (8 * y)) & 0xFFu);
@@ -298,7 +257,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
         const uint64_t wi = w0 + lane;
         uint64_t v = 0;
         if (wi < nw) {
-          v = ac_mask(ac_word(q, sh, wi), len - 8 * wi);
+          v = mask_low(word_at(q, sh, wi), len - 8 * wi);
           d[wi] = v;
         }
         const uint32_t m = (uint32_t)(nw - w0 < 64 ? nw - w0 : 64);
@@ -322,11 +281,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
 namespace mox_host {
 
 void accum_free(mox_engine* e) {
-  for (DevBuf* b : {&e->a_tab[0], &e->a_tab[1], &e->a_tab[2], &e->a_tc}) {
-    dfree(b->p);
-    b->p = nullptr;
-    b->cap = 0;
-  }
+  free_bufs({&e->a_tab[0], &e->a_tab[1], &e->a_tab[2], &e->a_tc});
   if (e->h_actot) (void)hipHostFree(e->h_actot);
   e->h_actot = nullptr;
   e->acc = mox_engine::Acc{};
@@ -344,26 +299,13 @@ AcTab ac_tab(const uint64_t* counts, const uint64_t* offs, const uint8_t* bytes,
 // nothing else is left of the result).
 void acc_as_result(mox_engine* e) {
   mox_engine::Res& r = e->res;
-  r.counts = (const uint64_t*)e->a_tab[0].p;
-  r.offs = (const uint64_t*)e->a_tab[1].p;
-  r.bytes = (const uint8_t*)e->a_tab[2].p;
-  r.n = e->acc.n;
-  r.nb = e->acc.nb;
-  r.tokens = e->acc.tokens;
+  res_point_at(r, e->a_tab, e->acc.n, e->acc.nb, e->acc.tokens);
   r.pass = false;
   r.exchanged = false;
   r.sorted = e->acc.sorted;
   r.ranked = e->acc.ranked;
   r.folded = true;
   e->have_result = true;
-}
-
-// Buffers for a total of n rows and nb bytes into b[0..2] (a_bytes' layout:
-// 64 bytes of slack for the packer's aligned loads).
-int acc_reserve(DevBuf* b, uint64_t n, uint64_t nb) {
-  int rc;
-  if ((rc = grow_dev(b[0], 8 * n + 64)) || (rc = grow_dev(b[1], 8 * (n + 1) + 64)) || (rc = grow_dev(b[2], nb + 64))) return rc;
-  return MOX_OK;
 }
 
 // total := the engine's result (device to device), into buffers dst[0..2] that hold it.
@@ -450,11 +392,11 @@ int acc_merge(mox_engine* e, DevBuf* fresh, bool* use_fresh) {
   }
   // the new total has at most the rows and bytes of both tables
   const uint64_t un = ta.n + tb.n, ub = e->acc.nb + r.nb;
-  *use_fresh = e->a_tab[0].cap < 8 * un + 64 || e->a_tab[1].cap < 8 * (un + 1) + 64 || e->a_tab[2].cap < ub + 64;
-  if (*use_fresh && (rc = acc_reserve(fresh, un, ub))) return rc;
+  *use_fresh = e->a_tab[0].cap < 8 * un + TABLE_SLACK || e->a_tab[1].cap < 8 * (un + 1) + TABLE_SLACK || e->a_tab[2].cap < ub + TABLE_SLACK;
+  if (*use_fresh && (rc = table_reserve(fresh[0], fresh[1], fresh[2], un, ub))) return rc;
   HIPCHK(hipStreamSynchronize(s));  // both sources are packed: from here on the run's buffers may go
-  if (const char* f = getenv("MOX_TEST_FAIL_ACCUM"))
-    if (atoi(f)) return fail(MOX_ENOMEM, "accumulate: injected failure before the reduce pass (MOX_TEST_FAIL_ACCUM)");
+  if (test_fail_hook("MOX_TEST_FAIL_ACCUM"))
+    return fail(MOX_ENOMEM, "accumulate: injected failure before the reduce pass (MOX_TEST_FAIL_ACCUM)");
   mox_stats local = e->stats;
   local.weighted_records = rs + r_long;
   local.retries = 0;
@@ -473,7 +415,7 @@ int accumulate_impl(mox_engine* e) {
   DevBuf* cur = e->a_tab;
   if (!e->acc.have) {
     // an empty total: the result is saved as it is and stays the pass's own table
-    if (int rc = acc_reserve(cur, e->res.n, e->res.nb)) return rc;
+    if (int rc = table_reserve(cur[0], cur[1], cur[2], e->res.n, e->res.nb)) return rc;
     if (int rc = acc_save(e, cur)) return rc;
     acc_commit(e, 1);
     return MOX_OK;

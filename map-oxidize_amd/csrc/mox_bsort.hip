@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -65,8 +66,8 @@ __device__ __forceinline__ uint32_t digit_of(const BRec& r, int d) {
 }
 
 // Window bytes [WIN level, WIN level + WIN) of word i and its length class:
-// two aligned 8-byte loads and a funnel shift (the table's byte buffers carry
-// 64 bytes of slack past their end: grow_dev callers), not one load per byte.
+// two aligned 8-byte loads and a funnel shift (inside the table buffers' slack:
+// mox_dev.h), not one load per byte.
 __device__ __forceinline__ uint64_t window(const uint64_t* offs, const uint8_t* bytes, uint64_t i, uint32_t level) {
   const uint64_t o = offs[i], len = offs[i + 1] - o, a = (uint64_t)WIN * level;
   const uint64_t have = len > a ? len - a : 0;
@@ -164,11 +165,7 @@ extern "C" __global__ __launch_bounds__(256) void k_bs_gscan(const unsigned long
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   for (int d = 0; d < nd; d++) {
     const uint64_t x = gh[d * 256 + t];
-    uint64_t inc = x;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t y = __shfl_up(inc, o);
-      if (lane >= o) inc += y;
-    }
+    const uint64_t inc = wave_incscan<uint64_t>(x);
     if (lane == 63) ws[wv] = inc;
     __syncthreads();
     uint64_t pre = 0;
@@ -255,11 +252,7 @@ extern "C" __global__ __launch_bounds__(OS_THREADS, OS_WG_PER_CU) void k_os_pass
     cnt += c;
   }
   {
-    uint32_t inc = cnt;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(inc, o);
-      if (lane >= o) inc += y;
-    }
+    const uint32_t inc = wave_incscan<uint32_t>(cnt);
     if (lane == 63) ws[wv] = inc;
     __syncthreads();
     uint32_t pre = 0;
@@ -317,12 +310,7 @@ constexpr int SC1_T = 256, SC1_PER = 16, SC1_TILE = SC1_T * SC1_PER;
 constexpr int SC1_PAD = SC1_PER + 1;   // LDS row of a thread: 16 values + 1 pad
 constexpr uint64_t SC1_TOP = 4096;     // tile sums a workgroup reduces itself (16 per thread)
 __device__ __forceinline__ uint64_t wave_exscan64(uint64_t x, uint64_t& wave_tot) {
-  const int lane = threadIdx.x & 63;
-  uint64_t inc = x;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(inc, o);
-    if (lane >= o) inc += y;
-  }
+  const uint64_t inc = wave_incscan<uint64_t>(x);
   wave_tot = __shfl(inc, 63);
   return inc - x;
 }
@@ -715,11 +703,7 @@ int radix_sort(mox_engine* e, BSort& s, uint64_t n, int nd, bool zeroed) {
 }  // namespace
 
 void bsort_free(mox_engine* e) {
-  for (DevBuf* b : {&e->s_counts, &e->s_offs, &e->s_bytes, &e->s_tmp}) {
-    dfree(b->p);
-    b->p = nullptr;
-    b->cap = 0;
-  }
+  free_bufs({&e->s_counts, &e->s_offs, &e->s_bytes, &e->s_tmp});
   if (e->h_bsort) (void)hipHostFree(e->h_bsort);
   e->h_bsort = nullptr;
 }
@@ -772,8 +756,7 @@ int bsort_once(mox_engine* e, bool checked) {
   const uint64_t big[6] = {rec, rec, checked ? rec : 0, rec, u64n, u32n};
   uint8_t* bp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc;
-  if ((rc = grow_dev(e->s_counts, 8 * n + 64)) || (rc = grow_dev(e->s_offs, 8 * (n + 1) + 64)) || (rc = grow_dev(e->s_bytes, nb + 64)))
-    return rc;
+  if ((rc = table_reserve(e->s_counts, e->s_offs, e->s_bytes, n, nb))) return rc;
   uint64_t need = small;
   for (uint64_t b : big) need += b;
   rc = need > tmp_max ? (int)MOX_ENOMEM : grow_dev(e->s_tmp, need);

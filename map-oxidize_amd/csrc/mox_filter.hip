@@ -26,7 +26,7 @@
 //     read word bytes again to decide.  Per tile: kept rows, kept bytes, kept
 //     count sum.
 //  3. k_fl_scan (one workgroup): exclusive scans of the three tile arrays, the
-//     totals behind them (k_ac_scan's shape).  One 32-byte copy to the host
+//     totals behind them.  One 32-byte copy to the host
 //     sizes the output; MOX_FILTER_COUNT_ONLY ends here.
 //  4. k_fl_emit: a kept row's output index is its tile's scanned base, plus
 //     the wave totals before it (LDS), plus its ballot rank; its byte offset
@@ -40,10 +40,11 @@
 // Loads and stores: a word is copied as 8-byte words from its first byte on
 // (any alignment on either side), then a tail of 4, 2 and 1 bytes, so nothing
 // is read or written past a word: neighbouring output words belong to other
-// lanes.  Only the prefix load reads past a word, up to 15 bytes behind a
-// 1-byte last word; every bytes buffer a result can live in carries 64 bytes
-// of slack (see mox_accum.hip), the filter's own output buffers included, and
-// what is read past the prefix length is masked.
+// lanes (mox_dev.h: copy_lane, copy_wave).  Only the prefix load reads past a
+// word, up to 15 bytes behind a 1-byte last word: inside the slack of every
+// bytes buffer a result can live in (mox_dev.h: the slack contract), the
+// filter's own output buffers included, and what is read past the prefix
+// length is masked.
 //
 // Output: two sets of three buffers (mox_engine::f_tab); a call writes the set
 // the result does not live in, so a filtered result can be filtered again, and
@@ -58,6 +59,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -96,48 +98,6 @@ struct FlOut {
   uint64_t kept, bytes_kept;
 };
 
-// loads and stores of any alignment
-struct __attribute__((packed, aligned(1))) FlKey16 {
-  uint64_t lo, hi;
-};
-struct __attribute__((packed, aligned(1))) FlU64 {
-  uint64_t v;
-};
-struct __attribute__((packed, aligned(1))) FlU32 {
-  uint32_t v;
-};
-struct __attribute__((packed, aligned(1))) FlU16 {
-  uint16_t v;
-};
-
-__device__ __forceinline__ uint64_t fl_wave_sum64(uint64_t x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ __forceinline__ uint64_t fl_wave_incscan64(uint64_t x) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-// d[0, len) = s[0, len), by one lane: nothing outside the two ranges is touched
-__device__ __forceinline__ void fl_copy_lane(uint8_t* d, const uint8_t* s, uint64_t len) {
-  uint64_t x = 0;
-  for (; x + 8 <= len; x += 8) reinterpret_cast<FlU64*>(d + x)->v = reinterpret_cast<const FlU64*>(s + x)->v;
-  if (len & 4) {
-    reinterpret_cast<FlU32*>(d + x)->v = reinterpret_cast<const FlU32*>(s + x)->v;
-    x += 4;
-  }
-  if (len & 2) {
-    reinterpret_cast<FlU16*>(d + x)->v = reinterpret_cast<const FlU16*>(s + x)->v;
-    x += 2;
-  }
-  if (len & 1) d[x] = s[x];
-}
-
 }  // namespace
 
 // One bit per list word the table holds: idx[q] is the word's table index
@@ -156,7 +116,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_mark(const uint64_t* idx
       nf += (atomicOr(listed + (i >> 5), bit) & bit) ? 0u : 1u;
     }
   }
-  for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o);
+  nf = wave_sum(nf);
   if ((threadIdx.x & 63) == 0 && nf) atomicAdd(&s_nf, nf);
   __syncthreads();
   if (threadIdx.x == 0 && s_nf) atomicAdd(found, (unsigned long long)s_nf);
@@ -188,7 +148,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(FlTab T, FlPred P,
         if (k && P.plen) {
           k = len >= P.plen;  // a word shorter than the prefix is dropped
           if (k) {
-            const FlKey16 w = *reinterpret_cast<const FlKey16*>(T.bytes + o);
+            const Key16 w = *reinterpret_cast<const Key16*>(T.bytes + o);
             k = (w.lo & P.m0) == P.p0 && (w.hi & P.m1) == P.p1;
           }
         }
@@ -201,9 +161,9 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(FlTab T, FlPred P,
         cs += c;
       }
     }
-    nk = fl_wave_sum64(nk);
-    nb = fl_wave_sum64(nb);
-    cs = fl_wave_sum64(cs);
+    nk = wave_sum(nk);
+    nb = wave_sum(nb);
+    cs = wave_sum(cs);
     if (lane == 0) {
       s_w[wv][0] = nk;
       s_w[wv][1] = nb;
@@ -221,7 +181,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(FlTab T, FlPred P,
 
 // Exclusive scans in place of the three tile arrays; the totals at tc[3 nt +
 // k], k = kept rows, kept bytes, kept count sum.  One workgroup with a running
-// carry (k_ac_scan's shape); a step takes FL_SCAN_STEP tiles of all three
+// carry (mox_dev.h: scan_one_wg, widened); a step takes FL_SCAN_STEP tiles of all three
 // arrays, FL_SCAN_PER consecutive ones per thread, behind one pair of barriers
 // (one array after the other, 1,024 tiles per step, took 440 us for the 89,159
 // tiles of a 91 M-word table: 264 dependent steps).
@@ -239,7 +199,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_fl_scan(uint64_t* tc, uint6
       for (int j = 0; j < FL_SCAN_PER; j++)
         if (i0 + j < nt) s += tc[(uint64_t)k * nt + i0 + j];
       sum[k] = s;
-      inc[k] = fl_wave_incscan64(s);
+      inc[k] = wave_incscan<uint64_t>(s);
       if (lane == 63) ws[k][wv] = inc[k];
     }
     __syncthreads();
@@ -299,7 +259,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint
         len = __builtin_nontemporal_load(T.offs + i + 1) - o;
         cnt = __builtin_nontemporal_load(T.counts + i);
       }
-      const uint64_t inc = fl_wave_incscan64(len);
+      const uint64_t inc = wave_incscan<uint64_t>(len);
       __syncthreads();  // the previous round's s_w has been read (and s_nbig is zero)
       if (lane == 63) {
         s_w[wv][0] = (uint64_t)__popcll(m);
@@ -322,7 +282,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint
           out.counts[r] = cnt;
           out.offs[r] = bo;
           if (len <= FL_LANE_MAX) {
-            fl_copy_lane(out.bytes + bo, T.bytes + o, len);
+            copy_lane(out.bytes + bo, T.bytes + o, len);
           } else {  // a whole wave below
             const uint32_t x = atomicAdd(&s_nbig, 1u);
             s_big_b[x] = bo;
@@ -332,17 +292,12 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint
       }
     }
     __syncthreads();
-    // words over FL_LANE_MAX bytes: one wave each, 64 consecutive 8-byte words per step, then the tail bytes
+    // words over FL_LANE_MAX bytes: one wave each
     const uint32_t nbig = s_nbig;
     for (uint32_t x = wv; x < nbig; x += FL_WAVES) {
       const uint64_t i = base + s_big_k[x];
-      const uint64_t o = T.offs[i], len = T.offs[i + 1] - o;
-      const uint8_t* s = T.bytes + o;
-      uint8_t* d = out.bytes + s_big_b[x];
-      const uint64_t nw = len / 8;
-      for (uint64_t wi = lane; wi < nw; wi += 64)
-        reinterpret_cast<FlU64*>(d + 8 * wi)->v = reinterpret_cast<const FlU64*>(s + 8 * wi)->v;
-      if (lane < (len & 7)) d[8 * nw + lane] = s[8 * nw + lane];
+      const uint64_t o = T.offs[i];
+      copy_wave(out.bytes + s_big_b[x], T.bytes + o, T.offs[i + 1] - o);
     }
     __syncthreads();  // the LDS arrays are the next tile's
   }
@@ -351,10 +306,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint
 namespace mox_host {
 
 void filter_free(mox_engine* e) {
-  for (DevBuf* b : {&e->f_tab[0][0], &e->f_tab[0][1], &e->f_tab[0][2], &e->f_tab[1][0], &e->f_tab[1][1], &e->f_tab[1][2], &e->f_tmp}) {
-    dfree(b->p);
-    *b = DevBuf{};
-  }
+  free_bufs({&e->f_tab[0][0], &e->f_tab[0][1], &e->f_tab[0][2], &e->f_tab[1][0], &e->f_tab[1][1], &e->f_tab[1][2], &e->f_tmp});
   if (e->h_ftot) (void)hipHostFree(e->h_ftot);
   e->h_ftot = nullptr;
 }
@@ -418,10 +370,7 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   P.listed = listed;
   uint64_t* tot = e->h_ftot;  // kept rows, kept bytes, kept count sum, list words found
   for (int k = 0; k < 4; k++) tot[k] = 0;
-  uint64_t cap = 8ull * (uint64_t)e->n_cu;
-  if (const char* g = getenv("MOX_FILTER_GRID"))
-    if (atoll(g) > 0) cap = std::min<uint64_t>(cap, (uint64_t)atoll(g));
-  const uint32_t grid = (uint32_t)std::min(T.nt, cap);
+  const uint32_t grid = (uint32_t)std::min(T.nt, grid_cap(e, "MOX_FILTER_GRID"));
   if (T.n) {
     HIPCHK(hipMemsetAsync(tc + 3 * T.nt, 0, 64, st));
     if (P.list_mode) HIPCHK(hipMemsetAsync(listed, 0, bm_b, st));
@@ -458,11 +407,10 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
     return MOX_OK;
   };
   if (f->flags & MOX_FILTER_COUNT_ONLY) return finish();
-  if (const char* x = getenv("MOX_TEST_FAIL_FILTER"))
-    if (atoi(x)) return fail(MOX_ENOMEM, "filter: injected failure before the output is written (MOX_TEST_FAIL_FILTER)");
-  // the set of output buffers the result does not live in
-  DevBuf* dst = e->f_tab[(e->f_tab[0][0].p && r.counts == (const uint64_t*)e->f_tab[0][0].p) ? 1 : 0];
-  if ((rc = grow_dev(dst[0], 8 * tot[0] + 64)) || (rc = grow_dev(dst[1], 8 * (tot[0] + 1) + 64)) || (rc = grow_dev(dst[2], tot[1] + 64))) return rc;
+  if (test_fail_hook("MOX_TEST_FAIL_FILTER"))
+    return fail(MOX_ENOMEM, "filter: injected failure before the output is written (MOX_TEST_FAIL_FILTER)");
+  DevBuf* dst = table_other_set(e->f_tab, r);
+  if ((rc = table_reserve(dst[0], dst[1], dst[2], tot[0], tot[1]))) return rc;
   const FlOut out{(uint64_t*)dst[0].p, (uint64_t*)dst[1].p, (uint8_t*)dst[2].p, tot[0], tot[1]};
   if (T.n) {
     hipLaunchKernelGGL(k_fl_emit, dim3(grid), dim3(FL_T), 0, st, T, keep, tc, out);
@@ -474,12 +422,7 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   HIPCHK(hipStreamSynchronize(st));
   // the kept words are the result: order, sorted and folded as the source had them
   mox_engine::Res& res = e->res;
-  res.counts = out.counts;
-  res.offs = out.offs;
-  res.bytes = out.bytes;
-  res.n = tot[0];
-  res.nb = tot[1];
-  res.tokens = tot[2];
+  res_point_at(res, dst, tot[0], tot[1], tot[2]);
   res.pass = false;
   res.exchanged = false;
   return finish();

@@ -4,7 +4,9 @@
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
 // the device-resident accumulator (mox_accum.hip), the device lookup
 // (mox_lookup.hip), the device filter (mox_filter.hip) and the device ranking
-// (mox_rank.hip).
+// (mox_rank.hip).  The device-side helpers those kernels share are in
+// mox_dev.h; the host-side ones for their table buffers (table_reserve and
+// the declarations around it) are below.
 // Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -20,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -174,8 +177,8 @@ struct mox_engine {
     bool folded = false;     // true: already part of the accumulator (mox_accumulate takes a result once)
   } res;
   // mox_accumulate (mox_accum.hip): the running total as a saved table (a_tab:
-  // counts, offs, bytes; 64 bytes of slack each), the packer's tile counts and
-  // their pinned totals
+  // counts, offs, bytes; table_reserve), the packer's tile counts and their
+  // pinned totals
   struct Acc {
     bool have = false, sorted = false, ranked = false;
     uint64_t n = 0, nb = 0, tokens = 0, passes = 0;
@@ -195,8 +198,8 @@ struct mox_engine {
   // the pinned block the offsets go up and the outputs come back through
   DevBuf l_tmp, l_pin;
   // device filter (mox_filter.hip): two sets of output buffers (counts, offs,
-  // bytes; 64 bytes of slack each; a call writes the set the result does not
-  // live in), the scratch (tile arrays, keep masks, list bitmap) and the pinned totals
+  // bytes; table_reserve; a call writes the set the result does not live in:
+  // table_other_set), the scratch (tile arrays, keep masks, list bitmap) and the pinned totals
   DevBuf f_tab[2][3], f_tmp;
   uint64_t* h_ftot = nullptr;
   // device ranking (mox_rank.hip): two sets of output buffers (as f_tab), the
@@ -270,6 +273,20 @@ int stage_file_range(mox_engine* e, int fd, uint64_t off, size_t len);
 // ---- mox_multi.hip
 int grow_dev(DevBuf& b, size_t bytes);
 int grow_pinned(DevBuf& b, size_t bytes);
+void free_bufs(std::initializer_list<DevBuf*> bufs);  // device buffers: freed and reset
+// The slack every buffer of a result table carries past its contents (mox_dev.h:
+// what the kernels may read past a word because of it).
+constexpr size_t TABLE_SLACK = 64;
+// Buffers for a table of n rows and nb bytes.
+int table_reserve(DevBuf& counts, DevBuf& offs, DevBuf& bytes, uint64_t n, uint64_t nb);
+// Of two sets of table buffers (counts, offs, bytes), the one the result r does not live in.
+DevBuf* table_other_set(DevBuf (*sets)[3], const mox_engine::Res& r);
+// r's table is the one in set[0..2]; the order and state flags stay the caller's.
+void res_point_at(mox_engine::Res& r, DevBuf* set, uint64_t n, uint64_t nb, uint64_t tokens);
+// The grid cap of the kernels over table tiles: 8 workgroups per CU, or fewer with the environment variable env (tests).
+uint64_t grid_cap(const mox_engine* e, const char* env);
+// true when the environment variable env is a non-zero number: a call fails there on purpose (tests).
+bool test_fail_hook(const char* env);
 void group_destroy(mox_engine* e);
 int group_create(mox_engine* e, const mox_config* cfg);
 int group_count_host(mox_engine* e, const uint8_t* text, size_t len);

@@ -38,8 +38,8 @@
 //
 // Words of up to LK_LANE_MAX bytes are hashed and compared by their lane.
 // Longer ones (a table word reaches 16 MiB) are listed in LDS and taken by
-// whole waves afterwards, as mox_accum.hip's packer takes its big words: the
-// 64 lanes load 64 consecutive 8-byte words.  The hash is made for that: a sum
+// whole waves afterwards: the 64 lanes load 64 consecutive 8-byte words
+// (mox_dev.h: funnel).  The hash is made for that: a sum
 // over the word's 8-byte little-endian words (the last one masked by the
 // length) of a bijection of (word ^ position key), plus a multiple of the
 // length, then a 64-bit avalanche and fnv_finish (the forced-collision build
@@ -55,10 +55,10 @@
 // Loads: a word at byte offset o is read as aligned 8-byte words from o & ~7
 // and a funnel shift, up to 15 bytes past its end (k_lk_stream's path for
 // words of at most 16 bytes: the 16 bytes from o on, in one load of any
-// alignment).  Every bytes buffer a
-// result can live in carries 64 bytes of slack (see mox_accum.hip), and so
-// does the query buffer here; what is read past a word is masked before it is
-// used.  A zero-length word loads nothing.
+// alignment).  That is inside the slack of every bytes buffer a result can
+// live in (mox_dev.h: the slack contract), which the query buffer here
+// carries too; what is read past a word is masked before it is used.  A
+// zero-length word loads nothing.
 //
 // Scratch (mox_engine::l_tmp, l_pin) is O(n + query bytes): the output block,
 // the representatives, the query offsets and bytes and the slots.  Nothing is
@@ -71,6 +71,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -126,12 +127,6 @@ constexpr uint64_t LK_MUL = 0xFF51AFD7ED558CCDull;
 constexpr uint64_t LK_MUL2 = 0xC4CEB9FE1A85EC53ull;
 constexpr uint64_t LK_LEN = 0x9E3779B97F4A7C15ull;
 
-// the 16 bytes from any byte address on, in one load
-struct __attribute__((packed, aligned(1))) LkKey16 {
-  uint64_t lo, hi;
-};
-__device__ __forceinline__ uint64_t lk_mask(uint64_t x, uint64_t n) { return n >= 8 ? x : x & ((1ull << (8 * n)) - 1ull); }
-__device__ __forceinline__ uint64_t lk_funnel(uint64_t a, uint64_t b, uint32_t sh) { return sh ? (a >> sh) | (b << (64 - sh)) : a; }
 // one 8-byte word's share of the hash: a bijection of the word for each position
 __device__ __forceinline__ uint64_t lk_term(uint64_t v, uint64_t poskey) {
   const uint64_t x = (v ^ poskey) * LK_MUL;
@@ -146,10 +141,6 @@ __device__ __forceinline__ uint64_t lk_finish(uint64_t acc, uint64_t len) {
   h ^= h >> 33;
   return mox::fnv_finish(h);
 }
-__device__ __forceinline__ uint64_t lk_wave_sum64(uint64_t x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 
 // The hash of bytes[o, o + len), by one lane / by the 64 lanes of a wave
 // (WAVE: every lane of the wave calls with the same arguments).
@@ -161,13 +152,13 @@ __device__ __forceinline__ uint64_t lk_hash(const uint8_t* bytes, uint64_t o, ui
   if (WAVE) {
     const uint64_t nw = (len + 7) / 8;
     for (uint64_t wi = threadIdx.x & 63; wi < nw; wi += 64)
-      acc += lk_term(lk_mask(lk_funnel(q[wi], q[wi + 1], sh), len - 8 * wi), (wi + 1) * LK_POS);
-    acc = lk_wave_sum64(acc);
+      acc += lk_term(mask_low(funnel(q[wi], q[wi + 1], sh), len - 8 * wi), (wi + 1) * LK_POS);
+    acc = wave_sum(acc);
   } else if (len) {
     uint64_t a = q[0], pk = LK_POS;
     for (uint64_t x = 0; 8 * x < len; x++, pk += LK_POS) {
       const uint64_t b = q[x + 1];
-      acc += lk_term(lk_mask(lk_funnel(a, b, sh), len - 8 * x), pk);
+      acc += lk_term(mask_low(funnel(a, b, sh), len - 8 * x), pk);
       a = b;
     }
   }
@@ -185,7 +176,7 @@ __device__ __forceinline__ bool lk_equal(const uint8_t* A, uint64_t oa, const ui
     for (uint64_t w0 = 0; w0 < nw; w0 += 64) {
       const uint64_t wi = w0 + (threadIdx.x & 63);
       bool ne = false;
-      if (wi < nw) ne = lk_mask(lk_funnel(qa[wi], qa[wi + 1], sa) ^ lk_funnel(qb[wi], qb[wi + 1], sb), len - 8 * wi) != 0;
+      if (wi < nw) ne = mask_low(funnel(qa[wi], qa[wi + 1], sa) ^ funnel(qb[wi], qb[wi + 1], sb), len - 8 * wi) != 0;
       if (__ballot(ne)) return false;
     }
     return true;
@@ -194,7 +185,7 @@ __device__ __forceinline__ bool lk_equal(const uint8_t* A, uint64_t oa, const ui
   uint64_t a0 = qa[0], b0 = qb[0];
   for (uint64_t x = 0; 8 * x < len; x++) {
     const uint64_t a1 = qa[x + 1], b1 = qb[x + 1];
-    if (lk_mask(lk_funnel(a0, a1, sa) ^ lk_funnel(b0, b1, sb), len - 8 * x)) return false;
+    if (mask_low(funnel(a0, a1, sa) ^ funnel(b0, b1, sb), len - 8 * x)) return false;
     a0 = a1;
     b0 = b1;
   }
@@ -363,15 +354,15 @@ extern "C" __global__ __launch_bounds__(LK_T) void k_lk_stream(LkTab T, LkSet S)
       const bool pass = len[j] < 64 ? (lenmask >> len[j]) & 1ull : (longer && len[j] != ~0ull);
       fast[j] = pass && len[j] - 1 < 16;
       slow[j] = pass && !fast[j];
-      const LkKey16 k = *reinterpret_cast<const LkKey16*>(T.bytes + (fast[j] ? o[j] : 0ull));
+      const Key16 k = *reinterpret_cast<const Key16*>(T.bytes + (fast[j] ? o[j] : 0ull));
       w0[j] = k.lo;
       w1[j] = k.hi;
     }
 #pragma unroll
     for (int j = 0; j < LK_PER; j++) {
       const uint64_t l = fast[j] ? len[j] : 1ull;
-      uint64_t acc = lk_term(lk_mask(w0[j], l), LK_POS);  // lk_hash<false>, unrolled for at most two words
-      if (l > 8) acc += lk_term(lk_mask(w1[j], l - 8), 2 * LK_POS);
+      uint64_t acc = lk_term(mask_low(w0[j], l), LK_POS);  // lk_hash<false>, unrolled for at most two words
+      if (l > 8) acc += lk_term(mask_low(w1[j], l - 8), 2 * LK_POS);
       h[j] = lk_finish(acc, l);
       cur[j] = S.slots[h[j] & S.mask];
     }
@@ -466,7 +457,7 @@ extern "C" __global__ __launch_bounds__(LK_T) void k_lk_finish(LkSet S) {
   __shared__ uint32_t s_nf;
   if (threadIdx.x == 0) s_nf = 0;
   __syncthreads();
-  for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o);
+  nf = wave_sum(nf);
   if ((threadIdx.x & 63) == 0 && nf) atomicAdd(&s_nf, nf);
   __syncthreads();
   if (threadIdx.x == 0 && s_nf) atomicAdd(&S.ctl->found, (unsigned long long)s_nf);
@@ -475,8 +466,7 @@ extern "C" __global__ __launch_bounds__(LK_T) void k_lk_finish(LkSet S) {
 namespace mox_host {
 
 void lookup_free(mox_engine* e) {
-  dfree(e->l_tmp.p);
-  e->l_tmp = DevBuf{};
+  free_bufs({&e->l_tmp});
   if (e->l_pin.p) (void)hipHostFree(e->l_pin.p);
   e->l_pin = DevBuf{};
 }
@@ -512,7 +502,7 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
   // device scratch: [counts n | control block | index n] (the part that comes back) | rep | query offsets | slots | query bytes
   const uint64_t nslots = std::max<uint64_t>(LK_MIN_SLOTS, next_pow2(LK_SLOTS_PER_QUERY * n));
   const size_t out_b = 16 * n + sizeof(LkCtl), rep_b = (4 * n + 7) & ~(size_t)7, qo_b = 8 * (n + 1), sl_b = 8 * nslots;
-  if ((rc = grow_dev(e->l_tmp, out_b + rep_b + qo_b + sl_b + nb + 64))) return rc;
+  if ((rc = grow_dev(e->l_tmp, out_b + rep_b + qo_b + sl_b + nb + TABLE_SLACK))) return rc;  // (the query bytes are read as table bytes are)
   if ((rc = grow_pinned(e->l_pin, std::max(out_b, qo_b)))) return rc;
   uint8_t* p = (uint8_t*)e->l_tmp.p;
   LkSet S{};
@@ -541,9 +531,7 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
   hipLaunchKernelGGL(k_lk_build, dim3((uint32_t)std::min(qtiles, cap)), dim3(LK_T), 0, st, S);
   q.step("k_lk_build");
   if (r.n) {
-    uint64_t scap = cap;
-    if (const char* g = getenv("MOX_LOOKUP_GRID"))
-      if (atoll(g) > 0) scap = std::min<uint64_t>(cap, (uint64_t)atoll(g));
+    const uint64_t scap = grid_cap(e, "MOX_LOOKUP_GRID");
     const uint64_t ttiles = (r.n + LK_TILE - 1) / LK_TILE;
     const LkTab T{r.counts, r.offs, r.bytes, r.n};
     hipLaunchKernelGGL(k_lk_stream, dim3((uint32_t)std::min(ttiles, scap)), dim3(LK_T), 0, st, T, S);

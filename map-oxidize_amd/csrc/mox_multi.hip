@@ -49,6 +49,39 @@ int grow_pinned(DevBuf& b, size_t bytes) {
   b.cap = want;
   return MOX_OK;
 }
+void free_bufs(std::initializer_list<DevBuf*> bufs) {
+  for (DevBuf* b : bufs) {
+    dfree(b->p);
+    *b = DevBuf{};
+  }
+}
+int table_reserve(DevBuf& counts, DevBuf& offs, DevBuf& bytes, uint64_t n, uint64_t nb) {
+  int rc;
+  if ((rc = grow_dev(counts, 8 * n + TABLE_SLACK)) || (rc = grow_dev(offs, 8 * (n + 1) + TABLE_SLACK)) || (rc = grow_dev(bytes, nb + TABLE_SLACK)))
+    return rc;
+  return MOX_OK;
+}
+DevBuf* table_other_set(DevBuf (*sets)[3], const mox_engine::Res& r) {
+  return sets[(sets[0][0].p && r.counts == (const uint64_t*)sets[0][0].p) ? 1 : 0];
+}
+void res_point_at(mox_engine::Res& r, DevBuf* set, uint64_t n, uint64_t nb, uint64_t tokens) {
+  r.counts = (const uint64_t*)set[0].p;
+  r.offs = (const uint64_t*)set[1].p;
+  r.bytes = (const uint8_t*)set[2].p;
+  r.n = n;
+  r.nb = nb;
+  r.tokens = tokens;
+}
+uint64_t grid_cap(const mox_engine* e, const char* env) {
+  uint64_t cap = 8ull * (uint64_t)e->n_cu;
+  if (const char* g = getenv(env))
+    if (atoll(g) > 0) cap = std::min<uint64_t>(cap, (uint64_t)atoll(g));
+  return cap;
+}
+bool test_fail_hook(const char* env) {
+  const char* x = getenv(env);
+  return x && atoi(x);
+}
 
 // Moves per-peer byte ranges between ranks.  send/recv are device buffers;
 // off/len are per-peer byte offsets and sizes (len identical on both sides of
@@ -477,9 +510,7 @@ int gather_impl(mox_engine* e, int P, int me, int root, Transport& T) {
   e->stats.gather_bytes = me == root ? ro : block;
   if (me == root) {
     // 3. root: concatenate in rank order
-    if ((rc = grow_dev(e->g_counts, 8 * N + 64)) || (rc = grow_dev(e->g_offs, 8 * (N + 1) + 64)) ||
-        (rc = grow_dev(e->g_bytes, NBt + 64)))
-      return rc;
+    if ((rc = table_reserve(e->g_counts, e->g_offs, e->g_bytes, N, NBt))) return rc;
     const uint8_t* rb = (const uint8_t*)e->g_recv.p;
     for (int d = 0; d < P; d++) {
       const uint64_t bn = h_recv[d].n_short, bb = h_recv[d].n_long;
@@ -782,9 +813,8 @@ int group_gather(Group& G) {
   gd.base_b_total = NBt;
   HIPCHK(hipSetDevice(root->device));
   int rc;
-  if ((rc = grow_dev(root->g_counts, 8 * N + 64)) || (rc = grow_dev(root->g_offs, 8 * (N + 1) + 64)) ||
-      (rc = grow_dev(root->g_bytes, NBt + 64)) || (rc = grow_dev(root->g_recv, 8 * N + 64)))
-    return rc;
+  if ((rc = table_reserve(root->g_counts, root->g_offs, root->g_bytes, N, NBt))) return rc;
+  if ((rc = grow_dev(root->g_recv, 8 * N + 64))) return rc;  // (the members' offsets, staged)
   uint64_t* gc = (uint64_t*)root->g_counts.p;
   uint8_t* gb = (uint8_t*)root->g_bytes.p;
   uint8_t* go = (uint8_t*)root->g_recv.p;

@@ -44,13 +44,15 @@
 //     consecutive 8-byte words per step.
 //
 // Loads and stores: a word is copied as 8-byte words from its first byte on
-// (any alignment on either side), then a tail of 4, 2 and 1 bytes, so nothing
-// is read or written past a word.  Every index a kernel derives (a scattered
-// position, a source row, an output byte range) is checked against the table
-// before it is used.
+// (any alignment on either side), then a tail of 4, 2 and 1 bytes (mox_dev.h:
+// copy_lane, copy_wave), so nothing is read or written past a word.  Every
+// index a kernel derives (a scattered position, a source row, an output byte
+// range) is checked against the table before it is used.  The one-workgroup
+// scans are mox_dev.h's scan_one_wg: a step is RK_TOP_T tiles = 4.2 M rows, or
+// 16 times as many for the chunk sums (22 dependent steps for a 91 M-word table).
 //
-// Output: two sets of three buffers (mox_engine::r_tab, 64 bytes of slack
-// each); a call writes the set the result does not live in, so a ranked result
+// Output: two sets of three buffers (mox_engine::r_tab, sized by
+// table_reserve); a call writes the set the result does not live in, so a ranked result
 // can be ranked again, and e->res is repointed only when everything has
 // succeeded.  Scratch (r_tmp) is 24 bytes per row (two key and two index
 // arrays) plus 1 KiB per tile.
@@ -68,6 +70,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -120,31 +123,6 @@ struct RkOut {
   uint8_t* bytes;
 };
 
-// loads and stores of any alignment
-struct __attribute__((packed, aligned(1))) RkU64 {
-  uint64_t v;
-};
-struct __attribute__((packed, aligned(1))) RkU32 {
-  uint32_t v;
-};
-struct __attribute__((packed, aligned(1))) RkU16 {
-  uint16_t v;
-};
-
-__device__ __forceinline__ uint64_t rk_wave_sum64(uint64_t x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-template <typename T>
-__device__ __forceinline__ T rk_wave_incscan(T x) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const T y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
 // The lanes of the wave whose row is valid and whose digit equals this lane's
 // (0 for a lane without a row).  Every lane of the wave calls it.
 __device__ __forceinline__ uint64_t rk_peers(uint32_t d, bool valid) {
@@ -156,48 +134,6 @@ __device__ __forceinline__ uint64_t rk_peers(uint32_t d, bool valid) {
     p &= bit ? m : ~m;
   }
   return valid ? p : 0ull;
-}
-
-// d[0, len) = s[0, len), by one lane: nothing outside the two ranges is touched
-__device__ __forceinline__ void rk_copy_lane(uint8_t* d, const uint8_t* s, uint64_t len) {
-  uint64_t x = 0;
-  for (; x + 8 <= len; x += 8) reinterpret_cast<RkU64*>(d + x)->v = reinterpret_cast<const RkU64*>(s + x)->v;
-  if (len & 4) {
-    reinterpret_cast<RkU32*>(d + x)->v = reinterpret_cast<const RkU32*>(s + x)->v;
-    x += 4;
-  }
-  if (len & 2) {
-    reinterpret_cast<RkU16*>(d + x)->v = reinterpret_cast<const RkU16*>(s + x)->v;
-    x += 2;
-  }
-  if (len & 1) d[x] = s[x];
-}
-
-// Exclusive scan in place of a[0, m) by one workgroup of RK_TOP_T threads, one
-// value per thread and step, with a running carry (k_ac_scan's shape); *total =
-// the sum.  (A step is RK_TOP_T tiles = 4.2 M rows, or 16 times as many for the
-// chunk sums: 22 dependent steps for a 91 M-word table.)
-template <typename T>
-__device__ __forceinline__ void rk_scan_one_wg(T* a, uint64_t m, T* total) {
-  __shared__ T ws[RK_TOP_T / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  T carry = 0;
-  for (uint64_t c = 0; c < m; c += RK_TOP_T) {
-    const uint64_t i = c + threadIdx.x;
-    const T v = i < m ? a[i] : (T)0;
-    const T inc = rk_wave_incscan<T>(v);
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    T pre = 0, tot = 0;
-    for (int j = 0; j < RK_TOP_T / 64; j++) {
-      if (j < wv) pre += ws[j];
-      tot += ws[j];
-    }
-    if (i < m) a[i] = carry + pre + inc - v;
-    carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry;
 }
 
 }  // namespace
@@ -265,7 +201,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_scan_part(const uint32_t
 }
 
 // Exclusive scan in place of the nc chunk sums; cs[nc] = the total (the rows).
-extern "C" __global__ __launch_bounds__(RK_TOP_T) void k_rk_scan_top(uint32_t* cs, uint64_t nc) { rk_scan_one_wg<uint32_t>(cs, nc, cs + nc); }
+extern "C" __global__ __launch_bounds__(RK_TOP_T) void k_rk_scan_top(uint32_t* cs, uint64_t nc) { scan_one_wg<uint32_t, RK_TOP_T>(cs, nc, cs + nc); }
 
 // Exclusive scan in place of th[0, m): every chunk's own scan on top of its
 // scanned sum cs[chunk].
@@ -282,7 +218,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_scan_apply(uint32_t* __r
       v[j] = in ? th[i0 + j] : 0u;
       s += v[j];
     }
-    const uint32_t inc = rk_wave_incscan<uint32_t>(s);
+    const uint32_t inc = wave_incscan<uint32_t>(s);
     if (lane == 63) s_w[wv] = inc;
     __syncthreads();
     uint32_t run = cs[c] + inc - s;
@@ -362,7 +298,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_len(RkTab T, RkOrder O, 
         if (src < T.n) nb += T.offs[src + 1] - T.offs[src];
       }
     }
-    nb = rk_wave_sum64(nb);
+    nb = wave_sum(nb);
     if (lane == 0) s_w[wv] = nb;
     __syncthreads();
     if (t == 0) {
@@ -375,7 +311,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_len(RkTab T, RkOrder O, 
 }
 
 // Exclusive scan in place of the nt tile byte sums; tb[nt] = the table's bytes.
-extern "C" __global__ __launch_bounds__(RK_TOP_T) void k_rk_offs(uint64_t* tb, uint64_t nt) { rk_scan_one_wg<uint64_t>(tb, nt, tb + nt); }
+extern "C" __global__ __launch_bounds__(RK_TOP_T) void k_rk_offs(uint64_t* tb, uint64_t nt) { scan_one_wg<uint64_t, RK_TOP_T>(tb, nt, tb + nt); }
 
 // The table in the new order (tb: k_rk_offs' output).
 extern "C" __global__ __launch_bounds__(RK_T) void k_rk_emit(RkTab T, RkOrder O, const uint64_t* __restrict__ tb, RkOut out) {
@@ -401,7 +337,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_emit(RkTab T, RkOrder O,
         len = T.offs[src + 1] - o;
         cnt = O.keys ? (__builtin_nontemporal_load(O.keys + r) ^ O.flip) : T.counts[src];
       }
-      const uint64_t inc = rk_wave_incscan<uint64_t>(len);
+      const uint64_t inc = wave_incscan<uint64_t>(len);
       __syncthreads();  // the previous round's s_w and long-word list have been read
       if (lane == 63) s_w[wv] = inc;
       if (t == 0) s_nbig = 0;
@@ -417,7 +353,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_emit(RkTab T, RkOrder O,
           out.counts[r] = cnt;
           out.offs[r] = bo;
           if (len <= RK_LANE_MAX) {
-            rk_copy_lane(out.bytes + bo, T.bytes + o, len);
+            copy_lane(out.bytes + bo, T.bytes + o, len);
           } else {  // a whole wave below
             const uint32_t x = atomicAdd(&s_nbig, 1u);
             s_big_d[x] = bo;
@@ -427,16 +363,10 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_emit(RkTab T, RkOrder O,
         }
       }
       __syncthreads();
-      // words over RK_LANE_MAX bytes: one wave each, 64 consecutive 8-byte words per step, then the tail bytes
+      // words over RK_LANE_MAX bytes: one wave each
       const uint32_t nbig = s_nbig;
       for (uint32_t x = wv; x < nbig; x += RK_WAVES) {
-        const uint64_t len2 = s_big_l[x];
-        const uint8_t* s = T.bytes + s_big_s[x];
-        uint8_t* d = out.bytes + s_big_d[x];
-        const uint64_t nw = len2 / 8;
-        for (uint64_t wi = lane; wi < nw; wi += 64)
-          reinterpret_cast<RkU64*>(d + 8 * wi)->v = reinterpret_cast<const RkU64*>(s + 8 * wi)->v;
-        if (lane < (len2 & 7)) d[8 * nw + lane] = s[8 * nw + lane];
+        copy_wave(out.bytes + s_big_d[x], T.bytes + s_big_s[x], s_big_l[x]);
       }
     }
     __syncthreads();  // the LDS arrays are the next tile's
@@ -446,10 +376,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_emit(RkTab T, RkOrder O,
 namespace mox_host {
 
 void rank_free(mox_engine* e) {
-  for (DevBuf* b : {&e->r_tab[0][0], &e->r_tab[0][1], &e->r_tab[0][2], &e->r_tab[1][0], &e->r_tab[1][1], &e->r_tab[1][2], &e->r_tmp}) {
-    dfree(b->p);
-    *b = DevBuf{};
-  }
+  free_bufs({&e->r_tab[0][0], &e->r_tab[0][1], &e->r_tab[0][2], &e->r_tab[1][0], &e->r_tab[1][1], &e->r_tab[1][2], &e->r_tmp});
   if (e->h_rmax) (void)hipHostFree(e->h_rmax);
   e->h_rmax = nullptr;
 }
@@ -480,10 +407,7 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
     if (info) *info = ri;
     return MOX_OK;
   };
-  const bool fail_hook = [] {
-    const char* x = getenv("MOX_TEST_FAIL_RANK");
-    return x && atoi(x);
-  }();
+  const bool fail_hook = test_fail_hook("MOX_TEST_FAIL_RANK");
   const char* hook_msg = "rank: injected failure before the output is written (MOX_TEST_FAIL_RANK)";
   if (r.n <= 1) {  // nothing can move: no launch reads a row but the one count
     if (r.n) HIPCHK(hipMemcpyAsync(&ri.max_count, r.counts, 8, hipMemcpyDeviceToHost, st));
@@ -495,9 +419,7 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
     return finish();
   }
   const RkTab T{r.counts, r.offs, r.bytes, r.n, r.nb, (r.n + RK_TILE - 1) / RK_TILE};
-  uint64_t cap = 8ull * (uint64_t)e->n_cu;
-  if (const char* g = getenv("MOX_RANK_GRID"))
-    if (atoll(g) > 0) cap = std::min<uint64_t>(cap, (uint64_t)atoll(g));
+  const uint64_t cap = grid_cap(e, "MOX_RANK_GRID");
   const uint32_t grid = (uint32_t)std::min(T.nt, cap);
   // scratch: [block maxima] [keys A] [keys B] [rows A] [rows B] [digit counts 256 nt] [chunk sums nc + 1] [tile bytes nt + 1]
   // (every array a multiple of 256 bytes)
@@ -561,8 +483,8 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
   if (fail_hook) return fail(MOX_ENOMEM, "%s", hook_msg);
 
   // 4. the table, into the set of output buffers the result does not live in
-  DevBuf* dst = e->r_tab[(e->r_tab[0][0].p && r.counts == (const uint64_t*)e->r_tab[0][0].p) ? 1 : 0];
-  if ((rc = grow_dev(dst[0], 8 * T.n + 64)) || (rc = grow_dev(dst[1], 8 * (T.n + 1) + 64)) || (rc = grow_dev(dst[2], T.nb + 64))) return rc;
+  DevBuf* dst = table_other_set(e->r_tab, r);
+  if ((rc = table_reserve(dst[0], dst[1], dst[2], T.n, T.nb))) return rc;
   const RkOut out{(uint64_t*)dst[0].p, (uint64_t*)dst[1].p, (uint8_t*)dst[2].p};
   hipLaunchKernelGGL(k_rk_emit, dim3(grid), dim3(RK_T), 0, st, T, O, (const uint64_t*)tb, out);
   q.step("k_rk_emit");
@@ -570,9 +492,7 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
   HIPCHK(hipStreamSynchronize(st));
   // the same words and counts in the new order: tokens, n, the bytes and folded are the source's
   mox_engine::Res& res = e->res;
-  res.counts = out.counts;
-  res.offs = out.offs;
-  res.bytes = out.bytes;
+  res_point_at(res, dst, r.n, r.nb, r.tokens);
   res.pass = false;
   res.exchanged = false;
   res.sorted = false;

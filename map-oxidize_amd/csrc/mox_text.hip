@@ -44,6 +44,7 @@
 #include <cerrno>
 #include <cstdlib>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -97,27 +98,6 @@ __device__ __forceinline__ uint32_t tx_digits(uint64_t c) {
   return t + (v >= tx_pow10[t] ? 1u : 0u);
 }
 
-__device__ __forceinline__ uint64_t tx_wave_sum64(uint64_t x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ __forceinline__ uint64_t tx_wave_incscan64(uint64_t x) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-__device__ __forceinline__ uint32_t tx_wave_incscan32(uint32_t x) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
 // one text byte at text offset g, if the slice holds it
 __device__ __forceinline__ void tx_put(uint8_t* out, uint64_t lo, uint64_t hi, uint64_t g, uint8_t v) {
   if (g >= lo && g < hi) out[g - lo] = v;
@@ -138,34 +118,14 @@ extern "C" __global__ __launch_bounds__(TX_T) void k_tx_len(const uint64_t* __re
       const uint64_t i = base + (uint64_t)j * 64 + lane;
       if (i < end) s += 2u + tx_digits(__builtin_nontemporal_load(counts + i));
     }
-    s = tx_wave_sum64(s);
+    s = wave_sum(s);
     if (lane == 0) tlen[tile] = s + (offs[end] - offs[base]);
   }
 }
 
 // Exclusive scan of a[0, nt) in place, a[nt] = the total: one workgroup,
-// 1,024 values per step with a running carry (k_tk_scan's shape).
-extern "C" __global__ __launch_bounds__(1024) void k_tx_scan(uint64_t* a, uint64_t nt) {
-  __shared__ uint64_t ws[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint64_t c = 0; c < nt; c += 1024) {
-    const uint64_t i = c + threadIdx.x;
-    const uint64_t x = i < nt ? a[i] : 0ull;
-    const uint64_t inc = tx_wave_incscan64(x);
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-    for (int k = 0; k < 16; k++) {
-      if (k < wv) pre += ws[k];
-      tot += ws[k];
-    }
-    if (i < nt) a[i] = carry + pre + inc - x;
-    carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a[nt] = carry;
-}
+// 1,024 values per step with a running carry (mox_dev.h).
+extern "C" __global__ __launch_bounds__(1024) void k_tx_scan(uint64_t* a, uint64_t nt) { scan_one_wg<uint64_t, 1024>(a, nt, a + nt); }
 
 // Text bytes [lo, hi) into out[0, hi - lo): lo is a multiple of 16 and out is
 // 16-byte aligned, so a text offset and its address in out share their phase
@@ -220,7 +180,7 @@ extern "C" __global__ __launch_bounds__(TX_T) void k_tx_emit(const uint64_t* __r
         v[j] = s_ex[TX_PER * t + j];
         sum += v[j];
       }
-      const uint32_t inc = tx_wave_incscan32(sum);
+      const uint32_t inc = wave_incscan<uint32_t>(sum);
       if (lane == 63) s_ws[wv] = inc;
       __syncthreads();
       uint32_t run = inc - sum;
@@ -337,11 +297,7 @@ extern "C" __global__ __launch_bounds__(TX_T) void k_tx_emit(const uint64_t* __r
 namespace mox_host {
 
 void text_free(mox_engine* e) {
-  for (DevBuf* b : {&e->tx_pre, &e->tx_slice[0], &e->tx_slice[1]}) {
-    dfree(b->p);
-    b->p = nullptr;
-    b->cap = 0;
-  }
+  free_bufs({&e->tx_pre, &e->tx_slice[0], &e->tx_slice[1]});
   for (DevBuf& b : e->tx_pin) {
     if (b.p) (void)hipHostFree(b.p);
     b.p = nullptr;

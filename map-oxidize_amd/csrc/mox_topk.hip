@@ -39,6 +39,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "mox_dev.h"
 #include "mox_host.h"
 
 namespace {
@@ -66,20 +67,6 @@ static_assert(sizeof(TkCtl) == 64, "read back in one copy");
 struct __attribute__((aligned(16))) TkCand {
   uint64_t count, idx;
 };
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-// inclusive scan over the wave's lanes
-__device__ __forceinline__ uint64_t wave_incscan64(uint64_t x) {
-  const int lane = threadIdx.x & 63;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
 
 }  // namespace
 
@@ -149,7 +136,7 @@ extern "C" __global__ __launch_bounds__(TK_BINS) void k_tk_pick(int level, uint6
   const uint64_t rem = kk - ctl->above;
   const uint32_t bin = (uint32_t)(TK_BINS - 1 - t);
   const uint64_t x = hist[level * TK_BINS + bin];
-  uint64_t inc = wave_incscan64(x);
+  uint64_t inc = wave_incscan<uint64_t>(x);
   if ((t & 63) == 63) ws[wv] = inc;
   __syncthreads();
   for (int k = 0; k < wv; k++) inc += ws[k];
@@ -183,34 +170,14 @@ extern "C" __global__ __launch_bounds__(TK_T) void k_tk_ties(const uint64_t* __r
         }
       }
     }
-    eq = wave_sum64(eq);
+    eq = wave_sum(eq);
     if (lane == 0) tcnt[tile] = eq;
   }
 }
 
 // Exclusive scan of a[0, nt) in place, a[nt] = the total: one workgroup,
-// 1,024 values per step with a running carry (nt = n / TK_TILE values).
-extern "C" __global__ __launch_bounds__(1024) void k_tk_scan(uint64_t* a, uint64_t nt) {
-  __shared__ uint64_t ws[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  for (uint64_t c = 0; c < nt; c += 1024) {
-    const uint64_t i = c + threadIdx.x;
-    const uint64_t x = i < nt ? a[i] : 0ull;
-    const uint64_t inc = wave_incscan64(x);
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    uint64_t pre = 0, tot = 0;
-    for (int k = 0; k < 16; k++) {
-      if (k < wv) pre += ws[k];
-      tot += ws[k];
-    }
-    if (i < nt) a[i] = carry + pre + inc - x;
-    carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a[nt] = carry;
-}
+// 1,024 values per step with a running carry (mox_dev.h; nt = n / TK_TILE values).
+extern "C" __global__ __launch_bounds__(1024) void k_tk_scan(uint64_t* a, uint64_t nt) { scan_one_wg<uint64_t, 1024>(a, nt, a + nt); }
 
 // The tied words (count == T) of global tie rank < need, in index order, into
 // candidates [above, kk).  One wave per tile, 64 consecutive indices per step:
@@ -290,7 +257,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_tk_sort(const TkCand* cand,
       len = offs[w + 1] - o;
       o_src[i] = o;
     }
-    const uint64_t inc = wave_incscan64(len);
+    const uint64_t inc = wave_incscan<uint64_t>(len);
     if (lane == 63) ws[wv] = inc;
     __syncthreads();
     uint64_t pre = 0, tot = 0;
@@ -334,11 +301,7 @@ extern "C" __global__ __launch_bounds__(256) void k_tk_gather(uint64_t kk, const
 namespace mox_host {
 
 void topk_free(mox_engine* e) {
-  for (DevBuf* b : {&e->k_tmp, &e->k_out}) {
-    dfree(b->p);
-    b->p = nullptr;
-    b->cap = 0;
-  }
+  free_bufs({&e->k_tmp, &e->k_out});
 }
 
 }  // namespace mox_host
