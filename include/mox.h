@@ -546,6 +546,96 @@ int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* info /* may be
  * result. */
 int mox_fetch_rows(mox_engine* e, uint64_t first, uint64_t n, mox_table** out);
 
+/* ---- re-keying the device-resident result ---- */
+/* Replaces every word of the device-resident result by a byte window of
+ * itself and sums the rows whose windows are equal, on the GPU: "the", "the,",
+ * "(the)" and "the." become one row with the summed count.  The map's
+ * tokenisation is unchanged (split_whitespace + to_lowercase, as the
+ * reference); this call works on the table afterwards.  Nothing is fetched and
+ * no host pass runs over the table: six totals come back.  Afterwards
+ * mox_top_words, mox_write_result / mox_result_text, mox_lookup_words,
+ * mox_filter_result, mox_rank_result, mox_sort_result, mox_fetch_table /
+ * mox_fetch_rows and mox_accumulate work on the new table as on any result.
+ * Every rule is per word, over its bytes, verbatim:
+ *  1. Trim.  Leading bytes are dropped while the byte is < 128 and its bit is
+ *     set in the effective set; then trailing bytes the same way.  Bytes >= 128
+ *     are never stripped, so a UTF-8 sequence is never cut.  The effective set
+ *     is trim_set, or'd with the punctuation set when
+ *     MOX_REKEY_TRIM_ASCII_PUNCT is given: the 32 bytes of Rust's
+ *     char::is_ascii_punctuation (Python's string.punctuation), as masks
+ *     {MOX_REKEY_PUNCT_LO, MOX_REKEY_PUNCT_HI}.  Inner punctuation stays:
+ *     "don't", "a.b".
+ *  2. Cap (max_chars = K > 0).  A character start is a byte b with
+ *     (b & 0xC0) != 0x80; the window ends before the (K+1)-th character start
+ *     in the trimmed window.  Continuation bytes at the very front of the
+ *     window are kept.  For valid UTF-8 this is the first K characters; it is
+ *     defined for any bytes, as mox_reduce_pairs words may be anything.  No
+ *     second trim follows the cap: "a.b.c" with K = 2 gives "a.".
+ *  3. Drop.  An empty window drops the row; its count goes to tokens_dropped,
+ *     and tokens_out = tokens_in - tokens_dropped is the new result's tokens.
+ *  4. Reduce.  Rows with equal windows are summed as u64, wrapping as
+ *     elsewhere; a word present with count 0 stays present.  The new table is
+ *     what mox_reduce_pairs gives over the windowed rows, by the same
+ *     classification rule (1..16 bytes without NUL: a 16-byte key; everything
+ *     else: the long table), so a word may change class in either direction.
+ *     Order is engine order.
+ * State after a re-key that changed something: the result is a reduce pass's
+ * table, as after an accumulate merge: a pass's own table, not exchanged, not
+ * sorted, not ranked, so mox_exchange may start from it.  The folded state is
+ * kept: a re-keyed total that was already folded is not folded again
+ * (mox_accumulate returns MOX_ESTATE until a run or mox_accumulate_reset).
+ * The accumulator is untouched.  Re-keying commutes with sums, so callers
+ * re-key each run's result before mox_accumulate, or re-key once at the end;
+ * a re-key of the total followed by another fold merges into the un-re-keyed
+ * accumulator.
+ * Nothing to do: when words_changed == 0 no reduce runs, and the result, its
+ * order and all its flags (sorted, ranked, folded, pass, exchanged) are
+ * exactly what they were; *info is still filled.  The call is therefore
+ * idempotent at the cost of one pass over the table.  A spec with an empty
+ * effective set and no cap is the same case.
+ * Works on every form of result: a run's, mox_reduce_pairs, exchanged,
+ * gathered, mox_run_shards, sorted, ranked, filtered, the accumulator's total,
+ * a re-keyed one.  Completes pending asynchronous passes first.  An engine
+ * group: member 0's gathered result, on member 0.
+ * Distributed use: ranks re-key their local pass result and then
+ * mox_exchange (or mox_exchange_host): owners are chosen from the new keys, so
+ * the exchange sums the variants across ranks.
+ * info may be NULL.  Device memory: 48 bytes of scratch per 1024 words and the
+ * exchange's receive buffers (the windowed rows in wire form), held by the
+ * engine until mox_engine_destroy.  A lane walks a run of stripped bytes
+ * serially: a 100,000-byte word of dashes costs 100,000 steps on one lane.
+ * MOX_ESTATE: no result yet.  MOX_EINVAL: a NULL engine or spec, an unknown
+ * flag, a pad or reserved word that is not 0.  Any error before the reduce
+ * pass -- MOX_ENOMEM for the scratch or the wire buffers included -- leaves
+ * the result exactly as it was and *info untouched.  An error inside the
+ * reduce pass leaves the engine with no result, as a failed mox_reduce_pairs
+ * does (the source table's buffers are the pass's to overwrite; no copy is
+ * kept to buy more); the accumulator is intact.
+ * MOX_REKEY_GRID=<workgroups> (tests; read at each call) caps the grid of the
+ * passes over rows; MOX_TEST_FAIL_REKEY=1 (tests; read at each call) returns
+ * MOX_ENOMEM after the pack and before the reduce pass. */
+#define MOX_REKEY_TRIM_ASCII_PUNCT 0x1u  /* or Rust's char::is_ascii_punctuation set into trim_set */
+#define MOX_REKEY_PUNCT_LO 0xFC00FFFE00000000ull  /* the punctuation bytes below 64 */
+#define MOX_REKEY_PUNCT_HI 0x78000001F8000001ull  /* ... and from 64 on */
+typedef struct mox_rekey {
+  uint64_t trim_set[2];   /* bit (b & 63) of trim_set[b >> 6]: ASCII byte b (< 128) is stripped from both ends */
+  uint64_t max_chars;     /* then keep only the first max_chars characters; 0: no cap */
+  uint32_t flags;         /* MOX_REKEY_* ; unknown bits: MOX_EINVAL */
+  uint32_t pad;           /* must be 0 */
+  uint64_t reserved[4];   /* must be 0 */
+} mox_rekey;               /* 64 bytes */
+typedef struct mox_rekey_info {
+  uint64_t words_in, words_out;      /* rows before / after */
+  uint64_t words_changed;            /* rows whose window is not the whole word (dropped ones included) */
+  uint64_t words_dropped;            /* rows whose window is empty */
+  uint64_t tokens_in, tokens_out, tokens_dropped;
+  uint64_t bytes_out;                /* word bytes of the new table */
+  uint64_t device_bytes;             /* device memory the call holds afterwards */
+  double ms;                         /* wall time of the call */
+  uint64_t reserved[4];
+} mox_rekey_info;          /* 112 bytes */
+int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_info* info /* may be NULL */);
+
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

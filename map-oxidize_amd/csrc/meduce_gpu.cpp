@@ -27,6 +27,12 @@
 // mox_rank_result), after any filter and before the file is written:
 // final_result.txt is then the same from run to run.  Without the option
 // every output is what it always was.
+// --trim-punct re-keys the total on the device (mox_rekey_result with
+// MOX_REKEY_TRIM_ASCII_PUNCT): ASCII punctuation is stripped from both ends of
+// every word and the variants are summed ("the," and "(the)" count as "the"),
+// words of punctuation alone go.  It applies before --min-count, --stop and
+// --by-count, and before anything is written or printed.  Without the option
+// every output is what it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +52,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> words;
   unsigned long long min_count = 0;
   std::string stop_path;
-  bool have_stop = false, by_count = false;
+  bool have_stop = false, by_count = false, trim_punct = false;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
@@ -55,6 +61,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--min-count") && i + 1 < argc) min_count = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--stop") && i + 1 < argc) { stop_path = argv[++i]; have_stop = true; }
     else if (!strcmp(argv[i], "--by-count")) by_count = true;
+    else if (!strcmp(argv[i], "--trim-punct")) trim_punct = true;
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) paths.push_back("shakes.txt");
@@ -88,6 +95,12 @@ int main(int argc, char** argv) {
     rc = mox_run_file(e, paths[0].c_str());
   } else {
     for (size_t i = 0; i < paths.size() && rc == MOX_OK; i++) rc = mox_accumulate_file(e, paths[i].c_str(), chunk);
+  }
+  if (rc == MOX_OK && trim_punct) {
+    mox_rekey k;
+    memset(&k, 0, sizeof k);
+    k.flags = MOX_REKEY_TRIM_ASCII_PUNCT;
+    rc = mox_rekey_result(e, &k, nullptr);
   }
   if (rc == MOX_OK && (min_count || have_stop)) {
     mox_filter f;

@@ -1049,6 +1049,7 @@ void mox_engine_destroy(mox_engine* e) {
   lookup_free(e);
   filter_free(e);
   rank_free(e);
+  rekey_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

@@ -3,8 +3,8 @@
 // (mox_multi.hip), the device bytewise table sort (mox_bsort.hip) and the
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
 // the device-resident accumulator (mox_accum.hip), the device lookup
-// (mox_lookup.hip), the device filter (mox_filter.hip) and the device ranking
-// (mox_rank.hip).  The device-side helpers those kernels share are in
+// (mox_lookup.hip), the device filter (mox_filter.hip), the device ranking
+// (mox_rank.hip) and the device re-keying (mox_rekey.hip).  The device-side helpers those kernels share are in
 // mox_dev.h; the host-side ones for their table buffers (table_reserve and
 // the declarations around it) are below.
 // Internal: the public interface is include/mox.h.
@@ -207,6 +207,10 @@ struct mox_engine {
   // maxima / totals
   DevBuf r_tab[2][3], r_tmp;
   uint64_t* h_rmax = nullptr;
+  // device re-keying (mox_rekey.hip): the packer's tile counts and their pinned
+  // totals (the wire image goes to x_recv_short / x_recv_blob)
+  DevBuf q_tc;
+  uint64_t* h_qtot = nullptr;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -312,4 +316,6 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
 void filter_free(mox_engine* e);
 // ---- mox_rank.hip
 void rank_free(mox_engine* e);
+// ---- mox_rekey.hip
+void rekey_free(mox_engine* e);
 }  // namespace mox_host

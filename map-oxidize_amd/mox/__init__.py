@@ -43,6 +43,9 @@ FILTER_WORDS_KEEP = 1   # MOX_FILTER_WORDS_KEEP: only listed words survive (voca
 FILTER_COUNT_ONLY = 0x1  # MOX_FILTER_COUNT_ONLY: fill the info, leave the result as it is
 RANK_ASCENDING = 0x1  # MOX_RANK_ASCENDING: Engine.rank_result orders least frequent first
 RANK_MAX_WORDS = (1 << 32) - 1  # MOX_RANK_MAX_WORDS: the most words Engine.rank_result takes
+REKEY_TRIM_ASCII_PUNCT = 0x1  # MOX_REKEY_TRIM_ASCII_PUNCT: Engine.rekey_result strips ASCII punctuation
+# {MOX_REKEY_PUNCT_LO, MOX_REKEY_PUNCT_HI}: string.punctuation as a 128-bit set, bit (b & 63) of word b >> 6
+ASCII_PUNCT = (0xFC00FFFE00000000, 0x78000001F8000001)
 
 
 class MoxError(RuntimeError):
@@ -156,6 +159,34 @@ class RankInfo(ctypes.Structure):
     ]
 
 
+class Rekey(ctypes.Structure):
+    """mox_rekey: the spec of mox_rekey_result."""
+    _fields_ = [
+        ("trim_set", ctypes.c_uint64 * 2),
+        ("max_chars", ctypes.c_uint64),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class RekeyInfo(ctypes.Structure):
+    """mox_rekey_info: words in, out, changed and dropped, tokens in, out and dropped, bytes out, device bytes, ms."""
+    _fields_ = [
+        ("words_in", ctypes.c_uint64),
+        ("words_out", ctypes.c_uint64),
+        ("words_changed", ctypes.c_uint64),
+        ("words_dropped", ctypes.c_uint64),
+        ("tokens_in", ctypes.c_uint64),
+        ("tokens_out", ctypes.c_uint64),
+        ("tokens_dropped", ctypes.c_uint64),
+        ("bytes_out", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
 class _Table(ctypes.Structure):
     _fields_ = [
         ("n", ctypes.c_uint64),
@@ -263,6 +294,7 @@ def lib(path=None):
             "mox_filter_result": ([VP, P(Filter), P(FilterInfo)], I),
             "mox_rank_result": ([VP, ctypes.c_uint32, P(RankInfo)], I),
             "mox_fetch_rows": ([VP, U64, U64, P(P(_Table))], I),
+            "mox_rekey_result": ([VP, P(Rekey), P(RekeyInfo)], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -618,6 +650,26 @@ class Engine:
         t = ctypes.POINTER(_Table)()
         self._c(self._L.mox_fetch_rows(self._h, first, n, ctypes.byref(t)))
         return Table(t, self._L)
+
+    # -- the result re-keyed on the device (mox_rekey_result)
+    def rekey_result(self, trim=b"", punct=False, max_chars=0):
+        """Strip the ASCII characters of ``trim`` (bytes; with ``punct`` also
+        string.punctuation) from both ends of every word of the device-resident
+        result, keep the first ``max_chars`` characters (0: all) and sum the rows
+        that became equal, on the GPU; words left empty go (mox_rekey_result).
+        A byte >= 128 in ``trim`` raises ValueError.  Returns the info dict
+        {"words_in", "words_out", "words_changed", "words_dropped", "tokens_in",
+        "tokens_out", "tokens_dropped", "bytes_out", "device_bytes", "ms"}."""
+        k = Rekey()
+        for b in bytes(trim):
+            if b >= 128:
+                raise ValueError("trim holds the byte 0x%02x: only ASCII characters can be stripped" % b)
+            k.trim_set[b >> 6] |= 1 << (b & 63)
+        k.max_chars = max_chars
+        k.flags = REKEY_TRIM_ASCII_PUNCT if punct else 0
+        info = RekeyInfo()
+        self._c(self._L.mox_rekey_result(self._h, ctypes.byref(k), ctypes.byref(info)))
+        return {f: (float(info.ms) if f == "ms" else int(getattr(info, f))) for f, _ in info._fields_ if f != "reserved"}
 
     def stats(self):
         s = Stats()
