@@ -15,7 +15,7 @@ all: $(OUT)/libmox.so $(OUT)/libmox_corpus.so $(OUT)/meduce-gpu $(OUT)/libmox_ch
 $(OUT)/mox_kernels.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSRC)/mox_internal.h Makefile
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
-HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_dev.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
+HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_dev.h $(CSRC)/mox_pack.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
 $(OUT)/mox_engine.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -30,35 +30,38 @@
 //     a long word's byte offset a wave scan of the padded lengths: positions
 //     are deterministic and there is no global atomic anywhere.  Long words up
 //     to AC_COOP bytes are hashed and copied by their lane; longer ones are
-//     listed in LDS and taken by whole waves afterwards: the 64 lanes load 64
-//     consecutive 8-byte words (one coalesced 512-byte run), store them, and
-//     the hash walks the words lane by lane through v_readlane.  FNV-1a is a
-//     serial recurrence (h' = (h ^ b) * P), so only the loads and stores of a
-//     word spread over the lanes; its multiply chain does not.  The hash has to
-//     be the map's own (k_map's long lane), not merely some function of the
-//     bytes: after a fold the merge pass's long table feeds mox_exchange, which
-//     picks a long word's owner rank by this hash on every rank.
+//     listed in LDS and taken by whole waves afterwards, 64 consecutive 8-byte
+//     words per step.  The hash has to be the map's own (k_map's long lane),
+//     not merely some function of the bytes: after a fold the merge pass's
+//     long table feeds mox_exchange, which picks a long word's owner rank by
+//     this hash on every rank (mox_internal.h: fnv_step).
 //
-// Key loads: the 16 key bytes of a row at byte offset o come from three aligned
-// 8-byte loads at o & ~7 and a funnel shift, so they read up to 23 bytes past
-// o; a long word's copy reads whole 8-byte words the same way (mox_dev.h:
-// funnel, word_at).  That is inside the slack of every bytes buffer a result
+// The classifier, a round's ranks and both forms of the long-word copy + hash
+// are mox_pack.h's (pk_short, pk_ranks, pk_long_lane, pk_long_wave), which the
+// re-keying packer (mox_rekey.hip) uses too; the count kernel's sums, the scan,
+// the LDS list of big words and the tile loop are this file's.
+//
+// Key loads (mox_pack.h has the detail): the 16 key bytes of a row at byte
+// offset o come from three aligned 8-byte loads at o & ~7 and a funnel shift,
+// so they read up to 23 bytes past o; a long word's copy reads whole 8-byte
+// words the same way.  That is inside the slack of every bytes buffer a result
 // can live in (mox_dev.h: the slack contract), so no load leaves its
 // allocation and none is clamped.  What is read past a word is masked by the
 // word's length before the NUL test, the hash and every store.
 // A zero-length row (no result holds one) loads nothing: it becomes a header
 // with no bytes.
 //
-// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+// Resource usage (hipcc of ROCm 7.2.0: HIP 7.2.26015, AMD clang 22.0.0git
+// roc-7.2.0; the Makefile's flags, -Rpass-analysis=kernel-resource-usage):
 //   k_ac_count  38 VGPRs,  55 SGPRs,    96 B LDS, no scratch, no spills (8 waves / SIMD)
-//   k_ac_scan   66 VGPRs,  75 SGPRs,   128 B LDS, no scratch, no spills
-//   k_ac_pack   80 VGPRs, 106 SGPRs, 12392 B LDS, no scratch, no spills (6 waves / SIMD)
+//   k_ac_scan   92 VGPRs,  76 SGPRs,   128 B LDS, no scratch, no spills (one workgroup)
+//   k_ac_pack   86 VGPRs, 106 SGPRs, 12392 B LDS, no scratch, no spills (5 waves / SIMD)
 #include <algorithm>
 #include <cerrno>
 #include <cstdlib>
 
-#include "mox_dev.h"
 #include "mox_host.h"
+#include "mox_pack.h"
 
 namespace {
 
@@ -84,27 +87,6 @@ struct AcOut {
   uint64_t sbase[2], bbase[2], nlong[2];
 };
 
-constexpr uint64_t AC_FNV0 = 0xcbf29ce484222325ull;
-__device__ __forceinline__ uint64_t ac_fnv_step(uint64_t h, uint64_t b) { return (h ^ b) * 0x100000001b3ull; }
-__device__ __forceinline__ uint64_t ac_haszero(uint64_t v) { return (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull; }
-
-// Row classification.  len in 1..16: the key, masked by the length, and
-// whether it is NUL-free (bytes past the length are filled with ones for the
-// test).  Returns true for a short row (k0, k1 valid).
-__device__ __forceinline__ bool ac_short(const uint8_t* bytes, uint64_t o, uint64_t len, uint64_t& k0, uint64_t& k1) {
-  if (len - 1 >= 16) return false;  // 0 or > 16 bytes
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(bytes + (o & ~7ull));
-  const uint32_t sh = (uint32_t)(o & 7u) * 8u;
-  const uint64_t a = q[0], b = q[1], c = q[2];
-  k0 = sh ? (a >> sh) | (b << (64 - sh)) : a;  // (funnel, written out: three loads in flight whatever the length)
-  k1 = sh ? (b >> sh) | (c << (64 - sh)) : b;
-  k0 = mask_low(k0, len);
-  k1 = len > 8 ? mask_low(k1, len - 8) : 0ull;
-  const uint64_t f0 = len >= 8 ? 0ull : ~0ull << (8 * len);
-  const uint64_t f1 = len >= 16 ? 0ull : (len <= 8 ? ~0ull : ~0ull << (8 * (len - 8)));
-  return !(ac_haszero(k0 | f0) | ac_haszero(k1 | f1));
-}
-
 }  // namespace
 
 // tc[0 * nt + tile] = short rows, tc[1 * nt + tile] = long rows, tc[2 * nt +
@@ -124,7 +106,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(AcTab a, AcTab b, 
       if (i < s.n) {
         const uint64_t o = __builtin_nontemporal_load(s.offs + i), len = __builtin_nontemporal_load(s.offs + i + 1) - o;
         uint64_t k0, k1;
-        if (ac_short(s.bytes, o, len, k0, k1)) {
+        if (pk_short(s.bytes, o, len, k0, k1)) {
           ns++;
         } else {
           nl++;
@@ -166,7 +148,6 @@ extern "C" __global__ __launch_bounds__(1024) void k_ac_scan(uint64_t* tc, uint6
 // tc[3 nt + 6] is set when a short row has count 0 (such records need the
 // reduce pass's k_reduce_z; mox_kernels.hip).
 extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, uint64_t* __restrict__ tc, AcOut out) {
-  __shared__ uint64_t s_w[AC_WAVES][3];   // a round's short rows, long rows, long bytes per wave
   __shared__ uint64_t s_big_b[AC_TILE];   // long words over AC_COOP bytes: byte offset in the source's blob area,
   __shared__ uint16_t s_big_k[AC_TILE];   // ... row inside the tile
   __shared__ uint16_t s_big_r[AC_TILE];   // ... and header rank inside the tile
@@ -181,7 +162,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
     mox::WRec* S = out.shorts + out.sbase[si] + tc[tile];
     mox::XHdr* H = reinterpret_cast<mox::XHdr*>(out.blob + out.bbase[si]) + tc[nt + tile];
     uint8_t* area = out.blob + out.bbase[si] + out.nlong[si] * sizeof(mox::XHdr);
-    uint64_t rs = 0, rl = 0, rb = tc[2 * nt + tile];  // running short rank, long rank, byte offset
+    PkAt run{0, 0, tc[2 * nt + tile]};  // running short rank, long rank, byte offset
     if (t == 0) s_nbig = 0;
     for (int j = 0; j < AC_PER; j++) {
       const uint64_t i = base + (uint32_t)j * AC_T + t;
@@ -191,54 +172,21 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
         o = __builtin_nontemporal_load(s.offs + i);
         len = __builtin_nontemporal_load(s.offs + i + 1) - o;
         cnt = __builtin_nontemporal_load(s.counts + i);
-        is_s = ac_short(s.bytes, o, len, k0, k1);
+        is_s = pk_short(s.bytes, o, len, k0, k1);
         is_l = !is_s;
       }
-      const uint64_t ms = __ballot(is_s), ml = __ballot(is_l);
       if (__ballot(is_s && cnt == 0) && lane == 0) tc[3 * nt + 6] = 1;
-      const uint64_t below = lane ? ~0ull >> (64 - lane) : 0ull;
-      const uint64_t pl = is_l ? (len + 7) & ~7ull : 0ull;
-      const uint64_t inc = wave_incscan<uint64_t>(pl);
-      __syncthreads();  // the previous round's s_w has been read (and s_nbig is zero)
-      if (lane == 63) {
-        s_w[wv][0] = (uint64_t)__popcll(ms);
-        s_w[wv][1] = (uint64_t)__popcll(ml);
-        s_w[wv][2] = inc;
-      }
-      __syncthreads();
-      uint64_t ps = rs, pq = rl, pb = rb;
-      for (uint32_t k = 0; k < (uint32_t)AC_WAVES; k++) {
-        if (k < wv) {
-          ps += s_w[k][0];
-          pq += s_w[k][1];
-          pb += s_w[k][2];
-        }
-        rs += s_w[k][0];
-        rl += s_w[k][1];
-        rb += s_w[k][2];
-      }
+      const PkAt at = pk_ranks<AC_WAVES>(is_s, is_l, is_l ? (len + 7) & ~7ull : 0ull, run);
       if (is_s) {
-        S[ps + __popcll(ms & below)] = mox::WRec{k0, k1, cnt};
+        S[at.s] = mox::WRec{k0, k1, cnt};
       } else if (is_l) {
-        const uint64_t r = pq + __popcll(ml & below), bo = pb + inc - pl;
-        if (len <= AC_COOP) {  // this lane: 8-byte words, the last one masked (its pad bytes are zero)
-          const uint64_t* q = reinterpret_cast<const uint64_t*>(s.bytes + (o & ~7ull));
-          const uint32_t sh = (uint32_t)(o & 7u) * 8u;
-          uint64_t* d = reinterpret_cast<uint64_t*>(area + bo);
-          uint64_t h = AC_FNV0;
-          for (uint64_t x = 0; 8 * x < len; x++) {
-            const uint64_t m = len - 8 * x;
-            const uint64_t v = mask_low(word_at(q, sh, x), m);
-            d[x] = v;
-            const uint32_t nb = m < 8 ? (uint32_t)m : 8u;
-            for (uint32_t y = 0; y < nb; y++) h = ac_fnv_step(h, (v >> (8 * y)) & 0xFFu);
-          }
-          H[r] = mox::XHdr{mox::fnv_finish(h), len, cnt, bo};
+        if (len <= AC_COOP) {  // this lane
+          H[at.l] = mox::XHdr{pk_long_lane(s.bytes, o, len, area + at.b), len, cnt, at.b};
         } else {  // a whole wave below, which also writes the header
           const uint32_t x = atomicAdd(&s_nbig, 1u);
-          s_big_b[x] = bo;
+          s_big_b[x] = at.b;
           s_big_k[x] = (uint16_t)((uint32_t)j * AC_T + t);
-          s_big_r[x] = (uint16_t)r;  // r < AC_TILE
+          s_big_r[x] = (uint16_t)at.l;  // at.l < AC_TILE
         }
       }
     }
@@ -248,31 +196,8 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
     for (uint32_t x = wv; x < nbig; x += AC_WAVES) {
       const uint64_t i = base + s_big_k[x];
       const uint64_t o = s.offs[i], len = s.offs[i + 1] - o;
-      const uint64_t* q = reinterpret_cast<const uint64_t*>(s.bytes + (o & ~7ull));
-      const uint32_t sh = (uint32_t)(o & 7u) * 8u;
-      uint64_t* d = reinterpret_cast<uint64_t*>(area + s_big_b[x]);
-      const uint64_t nw = (len + 7) / 8;
-      uint64_t h = AC_FNV0;
-      for (uint64_t w0 = 0; w0 < nw; w0 += 64) {
-        const uint64_t wi = w0 + lane;
-        uint64_t v = 0;
-        if (wi < nw) {
-          v = mask_low(word_at(q, sh, wi), len - 8 * wi);
-          d[wi] = v;
-        }
-        const uint32_t m = (uint32_t)(nw - w0 < 64 ? nw - w0 : 64);
-        for (uint32_t l = 0; l < m; l++) {  // every lane walks the same chain: the word of lane l
-          const uint64_t u = __shfl(v, (int)l);
-          const uint64_t left = len - 8 * (w0 + l);
-          if (left >= 8) {
-#pragma unroll
-            for (uint32_t y = 0; y < 8; y++) h = ac_fnv_step(h, (u >> (8 * y)) & 0xFFu);
-          } else {
-            for (uint32_t y = 0; y < (uint32_t)left; y++) h = ac_fnv_step(h, (u >> (8 * y)) & 0xFFu);
-          }
-        }
-      }
-      if (lane == 0) H[s_big_r[x]] = mox::XHdr{mox::fnv_finish(h), len, s.counts[i], s_big_b[x]};
+      const uint64_t h = pk_long_wave(s.bytes, o, len, area + s_big_b[x]);
+      if (lane == 0) H[s_big_r[x]] = mox::XHdr{h, len, s.counts[i], s_big_b[x]};
     }
     __syncthreads();  // the LDS arrays are the next tile's
   }
@@ -282,8 +207,6 @@ namespace mox_host {
 
 void accum_free(mox_engine* e) {
   free_bufs({&e->a_tab[0], &e->a_tab[1], &e->a_tab[2], &e->a_tc});
-  if (e->h_actot) (void)hipHostFree(e->h_actot);
-  e->h_actot = nullptr;
   e->acc = mox_engine::Acc{};
 }
 
@@ -346,8 +269,7 @@ int acc_merge(mox_engine* e, DevBuf* fresh, bool* use_fresh) {
   hipStream_t s = e->stream;
   const Seq q = seq_of(e);
   int rc;
-  if (!e->h_actot) HIPCHK(hipHostMalloc((void**)&e->h_actot, 64, hipHostMallocDefault));
-  uint64_t* tot = e->h_actot;
+  uint64_t* tot = e->h_tot;
   for (int k = 0; k < 7; k++) tot[k] = 0;
   if ((rc = grow_dev(e->a_tc, (3 * nt + 8) * 8))) return rc;
   uint64_t* tc = (uint64_t*)e->a_tc.p;
@@ -366,22 +288,21 @@ int acc_merge(mox_engine* e, DevBuf* fresh, bool* use_fresh) {
     return fail(MOX_EHIP, "accumulate: inconsistent row counts (%llu + %llu of %llu, %llu + %llu of %llu)",
                 (unsigned long long)tot[0], (unsigned long long)tot[1], (unsigned long long)ta.n, (unsigned long long)tot[3],
                 (unsigned long long)tot[4], (unsigned long long)tb.n);
-  XDir rdir{};
-  rdir.P = 2;
+  Received rx;
+  rx.dir.P = 2;
   AcOut out{};
-  uint64_t rs = 0, rb = 0, r_long = 0;
   for (int k = 0; k < 2; k++) {
-    out.sbase[k] = rs;
-    out.bbase[k] = rdir.blob[k] = rb;
-    out.nlong[k] = rdir.nlong[k] = tot[3 * k + 1];
-    rdir.hpre[k] = r_long;
-    rs += tot[3 * k];
-    r_long += tot[3 * k + 1];
-    rb += tot[3 * k + 1] * sizeof(XHdr) + tot[3 * k + 2];
+    out.sbase[k] = rx.rs;
+    out.bbase[k] = rx.dir.blob[k] = rx.rb;
+    out.nlong[k] = rx.dir.nlong[k] = tot[3 * k + 1];
+    rx.dir.hpre[k] = rx.r_long;
+    rx.rs += tot[3 * k];
+    rx.r_long += tot[3 * k + 1];
+    rx.rb += tot[3 * k + 1] * sizeof(XHdr) + tot[3 * k + 2];
   }
-  rdir.blob[2] = rb;
-  rdir.hpre[2] = r_long;
-  if ((rc = grow_dev(e->x_recv_short, rs * sizeof(WRec) + 64)) || (rc = grow_dev(e->x_recv_blob, rb + 64))) return rc;
+  rx.dir.blob[2] = rx.rb;
+  rx.dir.hpre[2] = rx.r_long;
+  if ((rc = received_reserve(e, rx))) return rc;
   out.shorts = (WRec*)e->x_recv_short.p;
   out.blob = (uint8_t*)e->x_recv_blob.p;
   if (nt) {
@@ -397,14 +318,8 @@ int acc_merge(mox_engine* e, DevBuf* fresh, bool* use_fresh) {
   HIPCHK(hipStreamSynchronize(s));  // both sources are packed: from here on the run's buffers may go
   if (test_fail_hook("MOX_TEST_FAIL_ACCUM"))
     return fail(MOX_ENOMEM, "accumulate: injected failure before the reduce pass (MOX_TEST_FAIL_ACCUM)");
-  mox_stats local = e->stats;
-  local.weighted_records = rs + r_long;
-  local.retries = 0;
-  e->stats.retries = 0;
-  e->reduce_zero = tot[6] != 0;  // a short word with count 0 in either table: k_reduce_z
-  rc = reduce_received(e, rs, rb, r_long, rdir, local, t0);
-  e->reduce_zero = false;
-  return rc;
+  rx.zero = tot[6] != 0;  // a short word with count 0 in either table: k_reduce_z
+  return reduce_received(e, rx, packed_stats(e, rx), t0);
 }
 
 int accumulate_impl(mox_engine* e) {

@@ -1,8 +1,8 @@
 // Device-side helpers shared by the kernels over the device-resident result
 // table (counts, offs, bytes): mox_bsort.hip, mox_topk.hip, mox_text.hip,
-// mox_accum.hip, mox_lookup.hip, mox_filter.hip, mox_rank.hip, mox_rekey.hip.
-// Everything is
-// forced inline: a kernel that uses a helper compiles to what it compiled to
+// mox_accum.hip, mox_lookup.hip, mox_filter.hip, mox_rank.hip, mox_rekey.hip;
+// mox_pack.h builds the pieces of the two receive-layout packers on them.
+// Everything is forced inline: a kernel that uses a helper compiles to what it compiled to
 // with the helper's body written out.
 //
 // The slack contract.  Every bytes buffer a result can live in carries
@@ -12,10 +12,11 @@
 // past a word without a clamp as long as the read starts no later than the
 // word's first byte and ends less than TABLE_SLACK bytes past o.  The readers
 // that do: the 16 key bytes of a row as three aligned 8-byte loads from o & ~7
-// (the accumulate packer: up to 23 bytes past o; the re-keying packer the same
-// from a window's start, which lies inside the word), a word as aligned 8-byte
-// words from o & ~7 on (the packer's and the lookup's long words: up to 15
-// bytes past the word's end), the 16 bytes from o on in one load (the lookup's
+// (mox_pack.h's pk_short: up to 23 bytes past o for the accumulate packer; the
+// re-keying packer the same from a window's start, which lies inside the
+// word), a word as aligned 8-byte words from o & ~7 on (mox_pack.h's
+// pk_long_lane / pk_long_wave and the lookup's long words: up to 15 bytes past
+// the word's end), the 16 bytes from o on in one load (the lookup's
 // short path, the filter's prefix: up to 15 bytes past a 1-byte word) and the
 // sort's window (two aligned loads).  Whatever is read past a word is masked by
 // the word's length (mask_low) before it is used, and nothing is ever written

@@ -234,6 +234,7 @@ int alloc_fixed(mox_engine* e) {
   e->tables.n_ci = MOX_CI_N;
   HIPCHK(hipHostMalloc((void**)&e->h_ctl, sizeof(Ctl), hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void**)&e->h_ctl_init, sizeof(Ctl), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc((void**)&e->h_tot, 64, hipHostMallocDefault));
   memset(e->h_ctl_init, 0, sizeof(Ctl));
   e->h_ctl_init->err_utf8 = ~0ull;
   e->h_ctl_init->halo_err = ~0ull;
@@ -269,7 +270,7 @@ Seq seq_of(mox_engine* e) {
 
 // Stages 4-5 of a pass (shared by the corpus pass and the exchange pass):
 // shuffle directory + bucket reduce, then the dense table.
-void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q) {
+void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q, bool zero) {
   Work& w = e->w;
   hipStream_t s = e->stream;
   hipLaunchKernelGGL(k_hist, dim3(w.map_grid), dim3(1024), 0, s, w);  // last workgroup: partition offsets
@@ -287,7 +288,7 @@ void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q) {
   q.step("k_reduce_sort1");
   hipLaunchKernelGGL(k_reduce_sort2, dim3(8 * e->n_cu), dim3(64), 0, s, w);  // one wave per unit of 513..1024 records
   q.step("k_reduce_sort2");
-  hipLaunchKernelGGL(e->reduce_zero ? k_reduce_z : k_reduce, dim3(NB), dim3(RED_THREADS), reduce_lds_bytes(), s, w);  // workgroup b: partition b, then the work list
+  hipLaunchKernelGGL(zero ? k_reduce_z : k_reduce, dim3(NB), dim3(RED_THREADS), reduce_lds_bytes(), s, w);  // workgroup b: partition b, then the work list
   q.step("k_reduce");
   hipLaunchKernelGGL(k_reduce_small, dim3(8 * e->n_cu), dim3(128), 0, s, w);  // persistent, 8 per CU (SR_THREADS)
   q.step("k_reduce_small");
@@ -381,7 +382,7 @@ void enqueue_pass(mox_engine* e, const Corpus& c, const Seq& q, bool side = fals
   q.step("k_unicode");
   q.rec(3);
   // 4-5. shuffle directory + bucket reduce, table
-  launch_reduce_tail(e, c, q);
+  launch_reduce_tail(e, c, q, false);
 }
 
 int pipeline_once(mox_engine* e, const Corpus& c) {
@@ -978,7 +979,7 @@ int run_file_overlapped(mox_engine* e, int fd, size_t len) {
       q.rec(2);
       hipLaunchKernelGGL(k_unicode, dim3(1024), dim3(256), 0, s, whole, w, e->tables);
       q.rec(3);
-      launch_reduce_tail(e, whole, q);
+      launch_reduce_tail(e, whole, q, false);
     }
   }
   const int frc = st.finish();  // joins the readers: their error first
@@ -1081,6 +1082,7 @@ void mox_engine_destroy(mox_engine* e) {
   if (e->h_ctl_x) (void)hipHostFree(e->h_ctl_x);
   if (e->h_ctl) (void)hipHostFree(e->h_ctl);
   if (e->h_ctl_init) (void)hipHostFree(e->h_ctl_init);
+  if (e->h_tot) (void)hipHostFree(e->h_tot);
   for (auto& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (int t = 0; t < 16; t++) {
     if (e->file_stream[t]) (void)hipStreamDestroy(e->file_stream[t]);
@@ -1185,9 +1187,7 @@ static int sort_for_fetch(mox_engine* e, bool* host_sort) {
 int mox_fetch_table(mox_engine* e, mox_table** out) {
   if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
   *out = nullptr;
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
-  HIPCHK(hipSetDevice(e->device));
+  if (int rc = result_begin(e)) return rc;
   bool host_sort = false;
   if (int rc = sort_for_fetch(e, &host_sort)) return rc;
   const bool timing = (e->flags & MOX_F_TIMING) != 0;
@@ -1228,8 +1228,7 @@ int mox_fetch_table(mox_engine* e, mox_table** out) {
 
 int mox_sort_result(mox_engine* e) {
   if (!e) return fail(MOX_EINVAL, "NULL argument");
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  if (int rc = result_begin(e)) return rc;
   if (e->res.sorted) {  // (sorted and ranked at once: a table of at most one word)
     e->res.ranked = false;
     return MOX_OK;
@@ -1262,9 +1261,7 @@ static mox_table* table_of_rows(uint64_t cnt, uint64_t nbytes, uint64_t tokens) 
 int mox_fetch_rows(mox_engine* e, uint64_t first, uint64_t n, mox_table** out) {
   if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
   *out = nullptr;
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
-  HIPCHK(hipSetDevice(e->device));
+  if (int rc = result_begin(e)) return rc;
   bool host_sort = false;
   if (int rc = sort_for_fetch(e, &host_sort)) return rc;
   const mox_engine::Res& r = e->res;

@@ -307,8 +307,6 @@ namespace mox_host {
 
 void filter_free(mox_engine* e) {
   free_bufs({&e->f_tab[0][0], &e->f_tab[0][1], &e->f_tab[0][2], &e->f_tab[1][0], &e->f_tab[1][1], &e->f_tab[1][2], &e->f_tmp});
-  if (e->h_ftot) (void)hipHostFree(e->h_ftot);
-  e->h_ftot = nullptr;
 }
 
 }  // namespace mox_host
@@ -331,10 +329,8 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   for (uint64_t i = 0; i < nq; i++)
     if (f->word_offs[i + 1] < f->word_offs[i]) return fail(MOX_EINVAL, "filter: list offsets decrease at word %llu", (unsigned long long)i);
   if (nq && f->word_offs[nq] != f->word_offs[0] && !f->words) return fail(MOX_EINVAL, "filter: NULL words");
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  if (int rc = result_begin(e)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipSetDevice(e->device));
   const mox_engine::Res r = e->res;
   hipStream_t st = e->stream;
   const Seq q = seq_of(e);
@@ -363,12 +359,11 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   const FlTab T{r.counts, r.offs, r.bytes, r.n, (r.n + FL_TILE - 1) / FL_TILE};
   const size_t tc_b = (3 * T.nt + 8) * 8, keep_b = T.nt * FL_STEPS * 8, bm_b = P.list_mode ? ((r.n + 63) / 64) * 8 + 8 : 0;
   if ((rc = grow_dev(e->f_tmp, tc_b + keep_b + bm_b))) return rc;
-  if (!e->h_ftot) HIPCHK(hipHostMalloc((void**)&e->h_ftot, 64, hipHostMallocDefault));
   uint64_t* tc = (uint64_t*)e->f_tmp.p;
   uint64_t* keep = (uint64_t*)((uint8_t*)e->f_tmp.p + tc_b);
   uint32_t* listed = (uint32_t*)((uint8_t*)e->f_tmp.p + tc_b + keep_b);
   P.listed = listed;
-  uint64_t* tot = e->h_ftot;  // kept rows, kept bytes, kept count sum, list words found
+  uint64_t* tot = e->h_tot;  // kept rows, kept bytes, kept count sum, list words found
   for (int k = 0; k < 4; k++) tot[k] = 0;
   const uint32_t grid = (uint32_t)std::min(T.nt, grid_cap(e, "MOX_FILTER_GRID"));
   if (T.n) {

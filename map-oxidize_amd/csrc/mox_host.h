@@ -4,9 +4,10 @@
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
 // the device-resident accumulator (mox_accum.hip), the device lookup
 // (mox_lookup.hip), the device filter (mox_filter.hip), the device ranking
-// (mox_rank.hip) and the device re-keying (mox_rekey.hip).  The device-side helpers those kernels share are in
-// mox_dev.h; the host-side ones for their table buffers (table_reserve and
-// the declarations around it) are below.
+// (mox_rank.hip) and the device re-keying (mox_rekey.hip).  The device-side
+// helpers those kernels share are in mox_dev.h and mox_pack.h (the two
+// packers); the host-side ones (result_begin, table_reserve and the
+// declarations around it, Received: the hand-off to the reduce-only pass) are below.
 // Internal: the public interface is include/mox.h.
 #pragma once
 #include <fcntl.h>
@@ -154,6 +155,9 @@ struct mox_engine {
   Tables tables{};
   Ctl* h_ctl = nullptr;       // pinned
   Ctl* h_ctl_init = nullptr;  // pinned
+  // pinned, 64 bytes: the totals accumulate, filter and re-key read back (each
+  // runs on the engine's one host thread and has consumed them before it returns)
+  uint64_t* h_tot = nullptr;
   // engine-owned corpus staging for host inputs
   uint8_t* d_text = nullptr;
   size_t d_text_cap = 0;
@@ -177,15 +181,12 @@ struct mox_engine {
     bool folded = false;     // true: already part of the accumulator (mox_accumulate takes a result once)
   } res;
   // mox_accumulate (mox_accum.hip): the running total as a saved table (a_tab:
-  // counts, offs, bytes; table_reserve), the packer's tile counts and their
-  // pinned totals
+  // counts, offs, bytes; table_reserve) and the packer's tile counts
   struct Acc {
     bool have = false, sorted = false, ranked = false;
     uint64_t n = 0, nb = 0, tokens = 0, passes = 0;
   } acc;
   DevBuf a_tab[3], a_tc;
-  uint64_t* h_actot = nullptr;
-  bool reduce_zero = false;  // the reduce-only pass being launched holds weighted records with count 0: k_reduce_z
   DevBuf g_counts, g_offs, g_bytes, g_recv;  // mox_gather (root)
   DevBuf s_counts, s_offs, s_bytes, s_tmp;    // device bytewise sort (mox_bsort.hip): output + scratch
   unsigned long long* h_bsort = nullptr;      // pinned: the sort's digit histograms + totals
@@ -199,18 +200,16 @@ struct mox_engine {
   DevBuf l_tmp, l_pin;
   // device filter (mox_filter.hip): two sets of output buffers (counts, offs,
   // bytes; table_reserve; a call writes the set the result does not live in:
-  // table_other_set), the scratch (tile arrays, keep masks, list bitmap) and the pinned totals
+  // table_other_set) and the scratch (tile arrays, keep masks, list bitmap)
   DevBuf f_tab[2][3], f_tmp;
-  uint64_t* h_ftot = nullptr;
   // device ranking (mox_rank.hip): two sets of output buffers (as f_tab), the
   // scratch (keys, row indices, digit counts, tile bytes) and the pinned block
   // maxima / totals
   DevBuf r_tab[2][3], r_tmp;
   uint64_t* h_rmax = nullptr;
-  // device re-keying (mox_rekey.hip): the packer's tile counts and their pinned
-  // totals (the wire image goes to x_recv_short / x_recv_blob)
+  // device re-keying (mox_rekey.hip): the packer's tile counts (the wire image
+  // goes to x_recv_short / x_recv_blob)
   DevBuf q_tc;
-  uint64_t* h_qtot = nullptr;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -255,6 +254,15 @@ Caps grow_for(mox_engine* e, const Ctl& h);
 int check_failed(const Ctl& h);
 void set_result(mox_engine* e, const Ctl& h);
 int drain_async(mox_engine* e);
+// Opens a call over the result: pending async passes are completed, there is a
+// result, its device is current.  (Argument checks of the caller come first.)
+inline int result_begin(mox_engine* e) {
+  if (!e) return fail(MOX_EINVAL, "engine is NULL");
+  if (int rc = drain_async(e)) return rc;
+  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  HIPCHK(hipSetDevice(e->device));
+  return MOX_OK;
+}
 int run_corpus(mox_engine* e, const Corpus& c);
 Corpus make_corpus(const void* d_buf, size_t buf_len, size_t own_begin, size_t own_end, int at_end);
 // Launch sequencing helpers: HIP-event timestamps (MOX_F_TIMING) and, with
@@ -269,7 +277,8 @@ struct Seq {
   void step(const char* name) const;
 };
 Seq seq_of(mox_engine* e);
-void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q);
+// zero: the pass holds weighted records with count 0 (k_reduce_z instead of k_reduce; mox_kernels.hip)
+void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q, bool zero);
 int finish_pass(mox_engine* e, const Seq& q);
 int engine_create_one(const mox_config* cfg, int device, mox_engine** out);
 int stage_host_range(mox_engine* e, const uint8_t* text, size_t len);
@@ -296,8 +305,20 @@ int group_create(mox_engine* e, const mox_config* cfg);
 int group_count_host(mox_engine* e, const uint8_t* text, size_t len);
 int group_count_file(mox_engine* e, const char* path);
 int group_count_fd(mox_engine* e, int fd, uint64_t off, uint64_t len);  // bytes [off, off + len) of an open file
-int reduce_received(mox_engine* e, uint64_t rs, uint64_t rb, uint64_t r_long, const XDir& rdir, const mox_stats& local,
-                    std::chrono::steady_clock::time_point t0);
+// What a reduce-only pass takes over: rs WRecs in x_recv_short, rb bytes of
+// long-word blobs in x_recv_blob (r_long headers in all, laid out as dir says);
+// zero: a WRec may have count 0 (the pass takes k_reduce_z).
+struct Received {
+  uint64_t rs = 0, rb = 0, r_long = 0;
+  XDir dir{};
+  bool zero = false;
+};
+// One source (dir.P = 1): rs WRecs, r_long headers and behind them long_bytes bytes of words, each padded to 8.
+Received received_one(uint64_t rs, uint64_t r_long, uint64_t long_bytes, bool zero);
+int received_reserve(mox_engine* e, const Received& rx);  // x_recv_short / x_recv_blob hold what rx describes
+int reduce_received(mox_engine* e, const Received& rx, const mox_stats& local, std::chrono::steady_clock::time_point t0);
+// The stats the pass over a packed result starts from (accumulate, re-key): the run's, with rx's records and no retries.
+mox_stats packed_stats(mox_engine* e, const Received& rx);
 void xplan_free(mox_engine* e);
 // ---- mox_bsort.hip
 int bsort_table(mox_engine* e);  // the result table in bytewise order, on the device

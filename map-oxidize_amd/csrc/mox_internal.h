@@ -242,6 +242,14 @@ __host__ __device__ __forceinline__ uint32_t collide32(uint32_t h, int bits) {
   return h;
 #endif
 }
+// The long-word hash: FNV-1a-64 over the word's bytes, from FNV0, one fnv_step
+// per byte, then fnv_finish.  The map's long lane (mox_kernels.hip), the three
+// receive-layout packers (mox_pack.h for mox_accum.hip and mox_rekey.hip,
+// reduce_pairs_impl in mox_multi.hip) and mox_exchange's owner choice
+// (long_owner) must agree on it: a long word's owner rank is picked from this
+// hash on every rank.
+constexpr uint64_t FNV0 = 0xcbf29ce484222325ull;
+__host__ __device__ __forceinline__ uint64_t fnv_step(uint64_t h, uint8_t b) { return (h ^ b) * 0x100000001b3ull; }
 // Finish of the long-word FNV-1a-64 (host and device): identity in production.
 __host__ __device__ __forceinline__ uint64_t fnv_finish(uint64_t h) {
 #ifdef MOX_HASH_COLLIDE

@@ -53,8 +53,8 @@ __device__ __forceinline__ uint64_t lower_ascii(uint64_t x) {
 }
 __device__ __forceinline__ bool is_ascii_ws(uint32_t b) { return b == 0x20 || (b >= 9 && b <= 13); }
 __device__ __forceinline__ uint8_t ascii_lower(uint8_t b) { return (b >= 'A' && b <= 'Z') ? (uint8_t)(b + 32) : b; }
-__device__ __forceinline__ uint64_t fnv_step(uint64_t h, uint8_t b) { return (h ^ b) * 0x100000001b3ull; }
-constexpr uint64_t FNV0 = 0xcbf29ce484222325ull;
+// (the long-word hash, FNV0 and fnv_step: mox_internal.h, beside fnv_finish and
+// the list of those who must agree on it)
 
 __device__ __forceinline__ uint64_t lo_mask(int nbytes) {  // 0 <= nbytes <= 8
   return nbytes >= 8 ? ~0ull : ((1ull << (8 * nbytes)) - 1);

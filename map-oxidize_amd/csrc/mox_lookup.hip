@@ -486,15 +486,13 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
   if (n) nb = offs[n] - offs[0];
   if (nb >> 32) return fail(MOX_EINVAL, "lookup: %llu query bytes (fewer than 2^32)", (unsigned long long)nb);
   if (nb && !bytes) return fail(MOX_EINVAL, "lookup: NULL argument");
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  if (int rc = result_begin(e)) return rc;
   mox_lookup_info li{};
   li.queries = n;
   if (!n) {
     if (info) *info = li;
     return MOX_OK;
   }
-  HIPCHK(hipSetDevice(e->device));
   const mox_engine::Res& r = e->res;
   hipStream_t st = e->stream;
   const Seq q = seq_of(e);

@@ -189,7 +189,8 @@ struct HostTransport : Transport {
 };
 
 // One attempt of the reduce-only pass over the received partials.
-int exchange_pass_once(mox_engine* e, uint64_t r_short, uint64_t blob_bytes, const XDir& rdir) {
+int exchange_pass_once(mox_engine* e, const Received& rx) {
+  const uint64_t r_short = rx.rs, blob_bytes = rx.rb;
   Work& w = e->w;
   hipStream_t s = e->stream;
   const Seq q = seq_of(e);
@@ -200,17 +201,14 @@ int exchange_pass_once(mox_engine* e, uint64_t r_short, uint64_t blob_bytes, con
   if (blob_bytes) HIPCHK(hipMemcpyAsync(w.arena, e->x_recv_blob.p, blob_bytes, hipMemcpyDeviceToDevice, s));
   q.rec(1);
   q.rec(2);
-  hipLaunchKernelGGL(k_xingest, dim3(1024), dim3(256), 0, s, w, rdir, r_short);
+  hipLaunchKernelGGL(k_xingest, dim3(1024), dim3(256), 0, s, w, rx.dir, r_short);
   q.step("k_xingest");
   q.rec(3);
   Corpus none{};
   none.base = (const uint8_t*)w.ctl;  // long refs are all arena refs in this pass
-  launch_reduce_tail(e, none, q);
+  launch_reduce_tail(e, none, q, rx.zero);
   return finish_pass(e, q);
 }
-
-int reduce_received(mox_engine* e, uint64_t rs, uint64_t rb, uint64_t r_long, const XDir& rdir, const mox_stats& local,
-                    std::chrono::steady_clock::time_point t0);
 
 // The exchange in three phases, so that one process per GPU (exchange_impl,
 // with a Transport) and an engine group (group_exchange, every member's phase
@@ -399,7 +397,7 @@ int x_pack(mox_engine* e) {
 int x_reduce(mox_engine* e) {
   HIPCHK(hipSetDevice(e->device));
   const XPlan& x = *e->xp;
-  if (int rc = reduce_received(e, x.rs, x.rb, x.r_long, x.rdir, x.local, x.t0)) return rc;
+  if (int rc = reduce_received(e, Received{x.rs, x.rb, x.r_long, x.rdir, false}, x.local, x.t0)) return rc;
   e->stats.x_bytes_sent = x.ns * sizeof(WRec) + x.sb + x.P * sizeof(XCnt) + (x.ranged ? x.P * XS_BLOCK * 8 : 0);
   e->stats.x_bytes_recv = x.rs * sizeof(WRec) + x.rb + x.P * sizeof(XCnt) + (x.ranged ? x.P * XS_BLOCK * 8 : 0);
   e->res.exchanged = true;
@@ -1053,11 +1051,32 @@ int group_run_shards(mox_engine* e, const mox_shard* sh) {
   return group_run(e, c);
 }
 
-// Reduce-only pass over partial (word, count) records already in
-// x_recv_short (rs WRecs) and x_recv_blob (long-word blobs described by rdir):
-// the exchange's final reduce and mox_reduce_pairs (spill files) share it.
-int reduce_received(mox_engine* e, uint64_t rs, uint64_t rb, uint64_t r_long, const XDir& rdir, const mox_stats& local,
-                    std::chrono::steady_clock::time_point t0) {
+Received received_one(uint64_t rs, uint64_t r_long, uint64_t long_bytes, bool zero) {
+  Received rx{rs, r_long * sizeof(XHdr) + long_bytes, r_long, XDir{}, zero};
+  rx.dir.P = 1;
+  rx.dir.blob[1] = rx.rb;
+  rx.dir.nlong[0] = rx.dir.hpre[1] = r_long;
+  return rx;
+}
+
+int received_reserve(mox_engine* e, const Received& rx) {
+  if (int rc = grow_dev(e->x_recv_short, rx.rs * sizeof(WRec) + 64)) return rc;
+  return grow_dev(e->x_recv_blob, rx.rb + 64);
+}
+
+mox_stats packed_stats(mox_engine* e, const Received& rx) {
+  mox_stats local = e->stats;
+  local.weighted_records = rx.rs + rx.r_long;
+  local.retries = 0;
+  e->stats.retries = 0;
+  return local;
+}
+
+// Reduce-only pass over partial (word, count) records already in x_recv_short
+// and x_recv_blob, as rx describes them: the exchange's final reduce,
+// mox_reduce_pairs (spill files), mox_accumulate and mox_rekey_result share it.
+int reduce_received(mox_engine* e, const Received& rx, const mox_stats& local, std::chrono::steady_clock::time_point t0) {
+  const uint64_t rs = rx.rs, rb = rx.rb, r_long = rx.r_long;
   Work& w = e->w;
   int rc;
   Caps need = w.cold ? caps_of(w) : initial_caps(1 << 20, e->n_cu);
@@ -1069,7 +1088,7 @@ int reduce_received(mox_engine* e, uint64_t rs, uint64_t rb, uint64_t r_long, co
   e->have_result = false;
   if ((rc = ensure_caps(e, need))) return rc;  // stream-ordered; a regrow synchronises the device itself
   for (int attempt = 0;; attempt++) {
-    if ((rc = exchange_pass_once(e, rs, rb, rdir))) return rc;
+    if ((rc = exchange_pass_once(e, rx))) return rc;
     const Ctl& h = *e->h_ctl;
     if (e->verbose)  // the unit summary of run_corpus's attempt line, for the reduce-only pass
       fprintf(stderr, "[mox] reduce-only attempt %d: overflow 0x%x w_total %llu n_total %llu; units %llu, sort2 list %llu, k_reduce list %llu, k_reduce_small list %llu, split partitions %u, max sub-passes %u\n",
@@ -1124,18 +1143,16 @@ int reduce_pairs_impl(mox_engine* e, const uint8_t* bytes, const uint64_t* offs,
       zero = zero || r.count == 0;
       shorts.push_back(r);
     } else {
-      uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a 64 (any hash works: all long words of this pass use it)
-      for (uint64_t j = 0; j < len; j++) h = (h ^ bytes[a + j]) * 0x100000001b3ull;
-      h = fnv_finish(h);
-      hdrs.push_back(XHdr{h, len, counts[i], (uint64_t)lbytes.size()});
+      uint64_t h = FNV0;  // the map's hash (mox_internal.h): an exchange after this pass picks owners by it
+      for (uint64_t j = 0; j < len; j++) h = fnv_step(h, bytes[a + j]);
+      hdrs.push_back(XHdr{fnv_finish(h), len, counts[i], (uint64_t)lbytes.size()});
       lbytes.insert(lbytes.end(), bytes + a, bytes + a + len);
       lbytes.resize((lbytes.size() + 7) & ~size_t(7), 0);
     }
   }
   const uint64_t rs = shorts.size(), r_long = hdrs.size();
-  const uint64_t rb = r_long * sizeof(XHdr) + lbytes.size();
-  int rc;
-  if ((rc = grow_dev(e->x_recv_short, rs * sizeof(WRec) + 64)) || (rc = grow_dev(e->x_recv_blob, rb + 64))) return rc;
+  const Received rx = received_one(rs, r_long, lbytes.size(), zero);
+  if (int rc = received_reserve(e, rx)) return rc;
   if (rs) HIPCHK(hipMemcpyAsync(e->x_recv_short.p, shorts.data(), rs * sizeof(WRec), hipMemcpyHostToDevice, e->stream));
   if (r_long) {
     HIPCHK(hipMemcpyAsync(e->x_recv_blob.p, hdrs.data(), r_long * sizeof(XHdr), hipMemcpyHostToDevice, e->stream));
@@ -1145,19 +1162,9 @@ int reduce_pairs_impl(mox_engine* e, const uint8_t* bytes, const uint64_t* offs,
   }
   // pageable sources: complete the copies before the vectors go away
   HIPCHK(hipStreamSynchronize(e->stream));
-  XDir rdir{};
-  rdir.P = 1;
-  rdir.blob[0] = 0;
-  rdir.blob[1] = rb;
-  rdir.nlong[0] = r_long;
-  rdir.hpre[0] = 0;
-  rdir.hpre[1] = r_long;
   mox_stats local{};
   local.weighted_records = rs + r_long;
-  e->reduce_zero = zero;
-  rc = reduce_received(e, rs, rb, r_long, rdir, local, t0);
-  e->reduce_zero = false;
-  return rc;
+  return reduce_received(e, rx, local, t0);
 }
 
 }  // namespace mox_host

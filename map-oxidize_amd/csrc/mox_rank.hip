@@ -386,10 +386,8 @@ void rank_free(mox_engine* e) {
 extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* info) {
   if (!e) return fail(MOX_EINVAL, "engine is NULL");
   if (flags & ~MOX_RANK_ASCENDING) return fail(MOX_EINVAL, "rank: unknown flags 0x%x", flags);
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  if (int rc = result_begin(e)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipSetDevice(e->device));
   const mox_engine::Res r = e->res;
   if (r.n > MOX_RANK_MAX_WORDS)
     return fail(MOX_EINVAL, "rank: %llu words (at most MOX_RANK_MAX_WORDS = 2^32 - 1)", (unsigned long long)r.n);

@@ -19,10 +19,11 @@
 // starts and is not walked.  The walks are serial, one byte per step: a
 // 100,000-byte word of dashes costs its lane 100,000 steps, as a long word's
 // hash already does.  A windowed row is classified by reduce_pairs_impl's rule
-// (1..16 bytes without a NUL byte -> a zero-padded WRec; every other -> an XHdr
-// with the map's FNV-1a-64 through fnv_finish, which mox_exchange picks owners
-// by, plus the bytes padded to 8); an empty window drops the row.  Tiles of
-// RQ_TILE consecutive rows, one workgroup per tile, grid-stride:
+// (1..16 bytes without a NUL byte -> a zero-padded WRec; every other -> an
+// XHdr{fnv_finish(h), length, count, offset} with h the map's FNV-1a-64, which
+// mox_exchange picks owners by, plus the bytes padded to 8); an empty window
+// drops the row.  Tiles of RQ_TILE consecutive rows, one workgroup per tile,
+// grid-stride:
 //
 //  1. k_rekey_count: per tile its short rows, long rows and padded long bytes,
 //     and the rows changed, the rows dropped and the counts dropped.
@@ -42,30 +43,36 @@
 //     A short windowed row with count 0 raises the flag behind the totals: the
 //     reduce pass then takes k_reduce_z.
 //
-// Key and word loads: as in the accumulator they are aligned 8-byte loads from
-// the start's word on, up to 23 bytes past the start, but the start is the
-// window's, which lies inside the word (a kept window has at least one byte).
-// It is therefore no later than the word's last byte, and the slack contract
-// (mox_dev.h) still covers the over-read: no load leaves its allocation.  What
-// is read past a window is masked by the window's length before the NUL test,
-// the hash and every store.  The window walks read single bytes of the word.
+// Key and word loads (mox_pack.h): as in the accumulator they are aligned
+// 8-byte loads from the start's word on, up to 23 bytes past the start, but the
+// start is the window's, which lies inside the word (a kept window has at least
+// one byte).  It is therefore no later than the word's last byte, and the slack
+// contract (mox_dev.h) still covers the over-read: no load leaves its
+// allocation.  What is read past a window is masked by the window's length
+// before the NUL test, the hash and every store.  The window walks read single
+// bytes of the word.
 //
-// The classifier and the packer body are copies of k_ac_count's / k_ac_pack's
-// rather than one template over a "row window": the count kernel sums six
-// values instead of three, the pack kernel drops rows and its wave pass derives
-// the window again, so a shared body would carry the window through k_ac_pack's
-// LDS list and registers.  mox_accum.hip is untouched and its kernels keep
-// their resource usage (38 and 80 VGPRs).
+// What the two packers have in common is in mox_pack.h, forced inline: the
+// short-row classifier (pk_short), a round's ranks (pk_ranks) and the copy +
+// hash of a long word by one lane and by a whole wave (pk_long_lane,
+// pk_long_wave); they take a byte range, so a window is an argument and nothing
+// else.  What differs stays here and is no template over a "row window": the
+// count kernel sums six values instead of three, the pack kernel drops rows and
+// its wave pass derives the window again, and a shared body would carry the
+// window through k_ac_pack's LDS list and registers.  So mox_accum.hip is
+// untouched by the window, and its kernels and this file's compile to the
+// resource usage they had with the pieces written out (profiles/pack/README.md).
 //
-// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+// Resource usage (hipcc of ROCm 7.2.0: HIP 7.2.26015, AMD clang 22.0.0git
+// roc-7.2.0; the Makefile's flags, -Rpass-analysis=kernel-resource-usage):
 //   k_rekey_count  56 VGPRs,  65 SGPRs,   192 B LDS, no scratch, no spills (8 waves / SIMD)
 //   k_rekey_scan  128 VGPRs,  72 SGPRs,   384 B LDS, no scratch, no spills (one workgroup)
 //   k_rekey_pack   84 VGPRs, 106 SGPRs, 12392 B LDS, no scratch, no spills (5 waves / SIMD)
 #include <algorithm>
 #include <cstdlib>
 
-#include "mox_dev.h"
 #include "mox_host.h"
+#include "mox_pack.h"
 
 namespace {
 
@@ -98,10 +105,6 @@ struct RqOut {
   uint64_t nlong;
 };
 
-constexpr uint64_t RQ_FNV0 = 0xcbf29ce484222325ull;
-__device__ __forceinline__ uint64_t rq_fnv_step(uint64_t h, uint64_t b) { return (h ^ b) * 0x100000001b3ull; }
-__device__ __forceinline__ uint64_t rq_haszero(uint64_t v) { return (v - 0x0101010101010101ull) & ~v & 0x8080808080808080ull; }
-
 __device__ __forceinline__ bool rq_trims(const RqSpec& P, uint32_t b) {
   return b < 128u && (((b < 64u ? P.set0 : P.set1) >> (b & 63u)) & 1ull);
 }
@@ -122,23 +125,6 @@ __device__ __forceinline__ void rq_window(const uint8_t* bytes, uint64_t o, uint
   }
   ws = s;
   wl = e - s;
-}
-
-// Classification of a window of len bytes at o (k_ac_count's rule).  len in
-// 1..16: the key, masked by the length, and whether it is NUL-free.  Returns
-// true for a short row (k0, k1 valid).
-__device__ __forceinline__ bool rq_short(const uint8_t* bytes, uint64_t o, uint64_t len, uint64_t& k0, uint64_t& k1) {
-  if (len - 1 >= 16) return false;  // 0 or > 16 bytes
-  const uint64_t* q = reinterpret_cast<const uint64_t*>(bytes + (o & ~7ull));
-  const uint32_t sh = (uint32_t)(o & 7u) * 8u;
-  const uint64_t a = q[0], b = q[1], c = q[2];
-  k0 = sh ? (a >> sh) | (b << (64 - sh)) : a;
-  k1 = sh ? (b >> sh) | (c << (64 - sh)) : b;
-  k0 = mask_low(k0, len);
-  k1 = len > 8 ? mask_low(k1, len - 8) : 0ull;
-  const uint64_t f0 = len >= 8 ? 0ull : ~0ull << (8 * len);
-  const uint64_t f1 = len >= 16 ? 0ull : (len <= 8 ? ~0ull : ~0ull << (8 * (len - 8)));
-  return !(rq_haszero(k0 | f0) | rq_haszero(k1 | f1));
 }
 
 }  // namespace
@@ -164,7 +150,7 @@ extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_count(RqTab T, RqSpec
           td += __builtin_nontemporal_load(T.counts + i);
         } else {
           nc += wl != len;
-          if (rq_short(T.bytes, ws, wl, k0, k1)) {
+          if (pk_short(T.bytes, ws, wl, k0, k1)) {
             ns++;
           } else {
             nl++;
@@ -277,7 +263,6 @@ extern "C" __global__ __launch_bounds__(1024) void k_rekey_scan(uint64_t* tc, ui
 // tc[6 nt + 6] is set when a short windowed row has count 0 (such records need
 // the reduce pass's k_reduce_z; mox_kernels.hip).
 extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(RqTab T, RqSpec P, uint64_t* __restrict__ tc, RqOut out) {
-  __shared__ uint64_t s_w[RQ_WAVES][3];   // a round's short rows, long rows, long bytes per wave
   __shared__ uint64_t s_big_b[RQ_TILE];   // long windows over RQ_COOP bytes: byte offset in the blob's word area,
   __shared__ uint16_t s_big_k[RQ_TILE];   // ... row inside the tile
   __shared__ uint16_t s_big_r[RQ_TILE];   // ... and header rank inside the tile
@@ -290,7 +275,7 @@ extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(RqTab T, RqSpec 
     const uint64_t base = tile * RQ_TILE;
     mox::WRec* S = out.shorts + tc[tile];
     mox::XHdr* H = H0 + tc[nt + tile];
-    uint64_t rs = 0, rl = 0, rb = tc[2 * nt + tile];  // running short rank, long rank, byte offset
+    PkAt run{0, 0, tc[2 * nt + tile]};  // running short rank, long rank, byte offset
     if (t == 0) s_nbig = 0;
     for (int j = 0; j < RQ_PER; j++) {
       const uint64_t i = base + (uint32_t)j * RQ_T + t;
@@ -301,55 +286,22 @@ extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(RqTab T, RqSpec 
         cnt = __builtin_nontemporal_load(T.counts + i);
         rq_window(T.bytes, o, len, P, ws, wl);
         if (wl) {  // (an empty window: the row is dropped)
-          is_s = rq_short(T.bytes, ws, wl, k0, k1);
+          is_s = pk_short(T.bytes, ws, wl, k0, k1);
           is_l = !is_s;
         }
       }
-      const uint64_t ms = __ballot(is_s), ml = __ballot(is_l);
       if (__ballot(is_s && cnt == 0) && lane == 0) tc[6 * nt + 6] = 1;
-      const uint64_t below = lane ? ~0ull >> (64 - lane) : 0ull;
-      const uint64_t pl = is_l ? (wl + 7) & ~7ull : 0ull;
-      const uint64_t inc = wave_incscan<uint64_t>(pl);
-      __syncthreads();  // the previous round's s_w has been read (and s_nbig is zero)
-      if (lane == 63) {
-        s_w[wv][0] = (uint64_t)__popcll(ms);
-        s_w[wv][1] = (uint64_t)__popcll(ml);
-        s_w[wv][2] = inc;
-      }
-      __syncthreads();
-      uint64_t ps = rs, pq = rl, pb = rb;
-      for (uint32_t k = 0; k < (uint32_t)RQ_WAVES; k++) {
-        if (k < wv) {
-          ps += s_w[k][0];
-          pq += s_w[k][1];
-          pb += s_w[k][2];
-        }
-        rs += s_w[k][0];
-        rl += s_w[k][1];
-        rb += s_w[k][2];
-      }
+      const PkAt at = pk_ranks<RQ_WAVES>(is_s, is_l, is_l ? (wl + 7) & ~7ull : 0ull, run);
       if (is_s) {
-        S[ps + __popcll(ms & below)] = mox::WRec{k0, k1, cnt};
+        S[at.s] = mox::WRec{k0, k1, cnt};
       } else if (is_l) {
-        const uint64_t r = pq + __popcll(ml & below), bo = pb + inc - pl;
-        if (wl <= RQ_COOP) {  // this lane: 8-byte words, the last one masked (its pad bytes are zero)
-          const uint64_t* q = reinterpret_cast<const uint64_t*>(T.bytes + (ws & ~7ull));
-          const uint32_t sh = (uint32_t)(ws & 7u) * 8u;
-          uint64_t* d = reinterpret_cast<uint64_t*>(area + bo);
-          uint64_t h = RQ_FNV0;
-          for (uint64_t x = 0; 8 * x < wl; x++) {
-            const uint64_t m = wl - 8 * x;
-            const uint64_t v = mask_low(word_at(q, sh, x), m);
-            d[x] = v;
-            const uint32_t nb = m < 8 ? (uint32_t)m : 8u;
-            for (uint32_t y = 0; y < nb; y++) h = rq_fnv_step(h, (v >> (8 * y)) & 0xFFu);
-          }
-          H[r] = mox::XHdr{mox::fnv_finish(h), wl, cnt, bo};
+        if (wl <= RQ_COOP) {  // this lane
+          H[at.l] = mox::XHdr{pk_long_lane(T.bytes, ws, wl, area + at.b), wl, cnt, at.b};
         } else {  // a whole wave below, which also writes the header
           const uint32_t x = atomicAdd(&s_nbig, 1u);
-          s_big_b[x] = bo;
+          s_big_b[x] = at.b;
           s_big_k[x] = (uint16_t)((uint32_t)j * RQ_T + t);
-          s_big_r[x] = (uint16_t)r;  // r < RQ_TILE
+          s_big_r[x] = (uint16_t)at.l;  // at.l < RQ_TILE
         }
       }
     }
@@ -361,31 +313,8 @@ extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(RqTab T, RqSpec 
       const uint64_t o = T.offs[i];
       uint64_t ws, wl;
       rq_window(T.bytes, o, T.offs[i + 1] - o, P, ws, wl);
-      const uint64_t* q = reinterpret_cast<const uint64_t*>(T.bytes + (ws & ~7ull));
-      const uint32_t sh = (uint32_t)(ws & 7u) * 8u;
-      uint64_t* d = reinterpret_cast<uint64_t*>(area + s_big_b[x]);
-      const uint64_t nw = (wl + 7) / 8;
-      uint64_t h = RQ_FNV0;
-      for (uint64_t w0 = 0; w0 < nw; w0 += 64) {
-        const uint64_t wi = w0 + lane;
-        uint64_t v = 0;
-        if (wi < nw) {
-          v = mask_low(word_at(q, sh, wi), wl - 8 * wi);
-          d[wi] = v;
-        }
-        const uint32_t m = (uint32_t)(nw - w0 < 64 ? nw - w0 : 64);
-        for (uint32_t l = 0; l < m; l++) {  // every lane walks the same chain: the word of lane l
-          const uint64_t u = __shfl(v, (int)l);
-          const uint64_t left = wl - 8 * (w0 + l);
-          if (left >= 8) {
-#pragma unroll
-            for (uint32_t y = 0; y < 8; y++) h = rq_fnv_step(h, (u >> (8 * y)) & 0xFFu);
-          } else {
-            for (uint32_t y = 0; y < (uint32_t)left; y++) h = rq_fnv_step(h, (u >> (8 * y)) & 0xFFu);
-          }
-        }
-      }
-      if (lane == 0) H[s_big_r[x]] = mox::XHdr{mox::fnv_finish(h), wl, T.counts[i], s_big_b[x]};
+      const uint64_t h = pk_long_wave(T.bytes, ws, wl, area + s_big_b[x]);
+      if (lane == 0) H[s_big_r[x]] = mox::XHdr{h, wl, T.counts[i], s_big_b[x]};
     }
     __syncthreads();  // the LDS arrays are the next tile's
   }
@@ -395,8 +324,6 @@ namespace mox_host {
 
 void rekey_free(mox_engine* e) {
   free_bufs({&e->q_tc});
-  if (e->h_qtot) (void)hipHostFree(e->h_qtot);
-  e->h_qtot = nullptr;
 }
 
 }  // namespace mox_host
@@ -408,10 +335,8 @@ extern "C" int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_inf
   if (k->pad) return fail(MOX_EINVAL, "rekey: pad is not 0");
   for (uint64_t r : k->reserved)
     if (r) return fail(MOX_EINVAL, "rekey: a reserved word is not 0");
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
+  if (int rc = result_begin(e)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  HIPCHK(hipSetDevice(e->device));
   const mox_engine::Res r = e->res;
   hipStream_t st = e->stream;
   const Seq q = seq_of(e);
@@ -424,9 +349,8 @@ extern "C" int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_inf
   const RqTab T{r.counts, r.offs, r.bytes, r.n, (r.n + RQ_TILE - 1) / RQ_TILE};
   const uint64_t nt = T.nt;
   if ((rc = grow_dev(e->q_tc, (6 * nt + 8) * 8))) return rc;
-  if (!e->h_qtot) HIPCHK(hipHostMalloc((void**)&e->h_qtot, 64, hipHostMallocDefault));
   uint64_t* tc = (uint64_t*)e->q_tc.p;
-  uint64_t* tot = e->h_qtot;  // short rows, long rows, padded long bytes, rows changed, rows dropped, counts dropped, zero flag
+  uint64_t* tot = e->h_tot;  // short rows, long rows, padded long bytes, rows changed, rows dropped, counts dropped, zero flag
   for (int i = 0; i < 7; i++) tot[i] = 0;
   const uint32_t grid = (uint32_t)std::min(nt, grid_cap(e, "MOX_REKEY_GRID"));
   if (nt) {
@@ -458,9 +382,9 @@ extern "C" int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_inf
     return MOX_OK;
   };
   if (!tot[3]) return finish();  // every window is its whole word: the result, its order and its flags stay
-  const uint64_t rs = tot[0], r_long = tot[1], rb = r_long * sizeof(XHdr) + tot[2];
-  if ((rc = grow_dev(e->x_recv_short, rs * sizeof(WRec) + 64)) || (rc = grow_dev(e->x_recv_blob, rb + 64))) return rc;
-  const RqOut out{(WRec*)e->x_recv_short.p, (uint8_t*)e->x_recv_blob.p, r_long};
+  Received rx = received_one(tot[0], tot[1], tot[2], false);
+  if ((rc = received_reserve(e, rx))) return rc;
+  const RqOut out{(WRec*)e->x_recv_short.p, (uint8_t*)e->x_recv_blob.p, rx.r_long};
   hipLaunchKernelGGL(k_rekey_pack, dim3(grid), dim3(RQ_T), 0, st, T, P, tc, out);
   q.step("k_rekey_pack");
   HIPCHK(hipGetLastError());
@@ -468,21 +392,8 @@ extern "C" int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_inf
   HIPCHK(hipStreamSynchronize(st));  // the table is packed: from here on its buffers may go
   if (test_fail_hook("MOX_TEST_FAIL_REKEY"))
     return fail(MOX_ENOMEM, "rekey: injected failure before the reduce pass (MOX_TEST_FAIL_REKEY)");
-  XDir rdir{};
-  rdir.P = 1;
-  rdir.blob[0] = 0;
-  rdir.blob[1] = rb;
-  rdir.nlong[0] = r_long;
-  rdir.hpre[0] = 0;
-  rdir.hpre[1] = r_long;
-  mox_stats local = e->stats;
-  local.weighted_records = rs + r_long;
-  local.retries = 0;
-  e->stats.retries = 0;
-  e->reduce_zero = tot[6] != 0;
-  rc = reduce_received(e, rs, rb, r_long, rdir, local, t0);
-  e->reduce_zero = false;
-  if (rc) return rc;  // no result is left, as after a failed mox_reduce_pairs; the accumulator is intact
+  rx.zero = tot[6] != 0;  // a short windowed row with count 0: k_reduce_z
+  if ((rc = reduce_received(e, rx, packed_stats(e, rx), t0))) return rc;  // no result is left, as after a failed mox_reduce_pairs; the accumulator is intact
   // a reduce pass's table (set_result); a total that was folded stays folded
   e->res.folded = r.folded;
   e->res.tokens = ki.tokens_out;

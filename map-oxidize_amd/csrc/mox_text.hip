@@ -347,9 +347,7 @@ uint64_t slice_bytes() {
 // Everything before the text exists: pending passes, state, the sort that
 // MOX_F_SORT_BYTES asks for.
 int tx_prepare(mox_engine* e) {
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
-  HIPCHK(hipSetDevice(e->device));
+  if (int rc = result_begin(e)) return rc;
   if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted && !e->res.ranked) {
     const auto t0 = std::chrono::steady_clock::now();
     const int rc = bsort_table(e);

@@ -310,9 +310,7 @@ extern "C" int mox_top_words(mox_engine* e, size_t k, mox_table** out) {
   if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
   *out = nullptr;
   if (k > MOX_TOP_MAX) return fail(MOX_EINVAL, "k = %zu (at most MOX_TOP_MAX = %d)", k, MOX_TOP_MAX);
-  if (int rc = drain_async(e)) return rc;
-  if (!e->have_result) return fail(MOX_ESTATE, "no result: run first");
-  HIPCHK(hipSetDevice(e->device));
+  if (int rc = result_begin(e)) return rc;
   const mox_engine::Res& r = e->res;
   const uint64_t n = r.n, kk = std::min<uint64_t>(k, n);
   hipStream_t st = e->stream;
