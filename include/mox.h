@@ -636,6 +636,76 @@ typedef struct mox_rekey_info {
 } mox_rekey_info;          /* 112 bytes */
 int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_info* info /* may be NULL */);
 
+/* ---- searching the sorted device-resident result ---- */
+/* Row ranges of n keys in the bytewise-sorted device-resident result, by binary
+ * search on the GPU: O(n log N) loads instead of a pass over the table.  Only
+ * the keys go to the device and two (or three) numbers per key come back.  Key
+ * i is bytes[offs[i], offs[i+1]), taken verbatim as mox_lookup_words takes its
+ * queries (not lowercased, not validated; any byte, 0x00 and 0xFF included).
+ * The order is the table's: Rust String Ord, bytes compared as unsigned, a
+ * proper prefix before the longer word ("ab" < "ab\0").
+ * first[i], last[i]: row indices into the table as it lies in device memory --
+ * exactly the rows mox_fetch_rows(first[i], last[i] - first[i]) returns and
+ * mox_top_rows selects from:
+ *   MOX_FIND_EXACT   the row whose word equals the key (last = first + 1),
+ *   MOX_FIND_PREFIX  the rows whose word starts with the key (an empty key:
+ *                    every row),
+ *   MOX_FIND_LOWER   first = last = the number of rows whose word is < key.
+ * An absent key gives first == last == its insertion point, in every mode.
+ * sums[i] (sums may be NULL): the wrapping u64 sum of counts[first, last) --
+ * EXACT: the word's count, PREFIX: the tokens under the prefix, LOWER: 0.
+ * With sums == NULL no kernel reads a count.  The sums are deterministic: no
+ * atomic adds a count.  info may be NULL.  With n == 0 nothing runs on the
+ * device and bytes, offs, first, last may be NULL.
+ * Needs a result in bytewise order: after mox_sort_result, a MOX_F_SORT_BYTES
+ * fetch, a ranged exchange or gather; a table of at most one word is in order
+ * as it is.  With MOX_F_SORT_BYTES set and a result neither sorted nor ranked
+ * the implicit device sort of mox_fetch_rows runs first; if that sort returns
+ * MOX_ENOMEM so does the call.  Any other result that is not in bytewise order
+ * (a ranked one included) is MOX_ESTATE: call mox_sort_result first.  Apart
+ * from that implicit sort the call only reads: result, accumulator and every
+ * state flag are unchanged.  Completes pending asynchronous passes first.  An
+ * engine group: member 0's gathered result.  After an exchange each rank owns
+ * a byte range of words, so the ranks' last - first and sums add up to the
+ * global figures without a gather.
+ * Cost: one lane per key, ceil(log2(N + 1)) steps of two offsets and the
+ * word's bytes, compared 8 bytes at a time up to the first difference (a long
+ * key against words that share its long prefix: O(len / 8) per step on that
+ * lane).  The sums read at most 2 x 1,023 counts per key directly; one
+ * streaming pass over the N counts (never over word bytes) is added only when
+ * some range holds a whole aligned tile of 1,024 rows (mox_find_info.tile_pass).
+ * Device scratch is O(n + key bytes + N / 1024), lives in the engine and is
+ * freed by mox_engine_destroy.
+ * MOX_ESTATE: no result yet, or a result not in bytewise order.  MOX_EINVAL: a
+ * NULL engine or required pointer, n > MOX_FIND_MAX, an unknown mode, offsets
+ * that decrease, or offs[n] - offs[0] >= 2^32 key bytes.  After any error the
+ * engine is usable and first, last, sums and info are untouched: they are
+ * written only after the last device check, and then completely.
+ * MOX_FIND_GRID=<workgroups> (tests; read at each call) caps every grid of the
+ * call, so that a small table and few keys run several grid strides. */
+#define MOX_FIND_EXACT  0u  /* the row whose word equals the key */
+#define MOX_FIND_PREFIX 1u  /* the rows whose word starts with the key (empty key: every row) */
+#define MOX_FIND_LOWER  2u  /* first = last = number of rows whose word is bytewise < key */
+#define MOX_FIND_MAX (1u << 20)
+typedef struct mox_find_info {
+  uint64_t queries, matched;   /* matched: queries with last > first */
+  uint64_t rows;               /* sum over queries of last - first */
+  uint64_t tile_pass;          /* 1: some range spanned a whole tile, the pass over the counts ran */
+  uint64_t device_bytes;       /* device memory the search holds after the call */
+  double ms;                   /* wall time of the call */
+  uint64_t reserved[4];
+} mox_find_info;
+int mox_find_ranges(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint32_t mode,
+                    uint64_t* first, uint64_t* last, uint64_t* sums /* may be NULL */, mox_find_info* info /* may be NULL */);
+/* mox_top_words over rows [first, min(first + n, N)) of the device-resident
+ * result: the k most frequent words among those rows, count descending, equal
+ * counts by table index ascending, tokens the whole result's total, k <=
+ * MOX_TOP_MAX.  Works on any result, sorted or not; with a range from
+ * mox_find_ranges(MOX_FIND_PREFIX) it is "the k most frequent words that start
+ * with ..." and never touches a row outside the range.  first >= N, n == 0 or
+ * k == 0: an empty table.  Errors as mox_top_words. */
+int mox_top_rows(mox_engine* e, uint64_t first, uint64_t n, size_t k, mox_table** out);
+
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

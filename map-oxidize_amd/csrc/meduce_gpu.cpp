@@ -33,6 +33,15 @@
 // words of punctuation alone go.  It applies before --min-count, --stop and
 // --by-count, and before anything is written or printed.  Without the option
 // every output is what it always was.
+// --prefix P (repeatable) prints, after everything else, "Prefix {P}: {rows}
+// words, {tokens} tokens" and up to ten "{word}: {count}" lines, the most
+// frequent words that start with P: the result is put in bytewise order on the
+// device if it is not (mox_sort_result; final_result.txt is then in that order
+// too, unless --by-count ranks it), two binary searches give P's row range and
+// the sum of its counts (mox_find_ranges) and the ten words are selected from
+// those rows alone (mox_top_rows).  The queries run after that sort and before
+// any --by-count ranking.  P is taken verbatim, as --word's W.  Without the
+// option every output is what it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
@@ -49,7 +58,7 @@ int main(int argc, char** argv) {
   std::string out = "final_result.txt";
   int device = -1;
   unsigned long long chunk = 0;
-  std::vector<std::string> words;
+  std::vector<std::string> words, prefixes;
   unsigned long long min_count = 0;
   std::string stop_path;
   bool have_stop = false, by_count = false, trim_punct = false;
@@ -58,6 +67,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
     else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) chunk = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--word") && i + 1 < argc) words.push_back(argv[++i]);
+    else if (!strcmp(argv[i], "--prefix") && i + 1 < argc) prefixes.push_back(argv[++i]);
     else if (!strcmp(argv[i], "--min-count") && i + 1 < argc) min_count = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--stop") && i + 1 < argc) { stop_path = argv[++i]; have_stop = true; }
     else if (!strcmp(argv[i], "--by-count")) by_count = true;
@@ -112,7 +122,21 @@ int main(int argc, char** argv) {
     f.words_mode = MOX_FILTER_WORDS_DROP;
     rc = mox_filter_result(e, &f, nullptr);
   }
-  if (rc == MOX_OK && by_count) rc = mox_sort_result(e);
+  if (rc == MOX_OK && (by_count || !prefixes.empty())) rc = mox_sort_result(e);
+  // the prefix queries, on the sorted table: the ranges, their tokens and their ten words (printed last)
+  std::vector<uint64_t> p_first(prefixes.size()), p_last(prefixes.size()), p_sums(prefixes.size());
+  std::vector<mox_table*> p_top(prefixes.size(), nullptr);
+  if (rc == MOX_OK && !prefixes.empty()) {
+    std::string bytes;
+    std::vector<uint64_t> offs(1, 0);
+    for (const std::string& p : prefixes) {
+      bytes += p;
+      offs.push_back(bytes.size());
+    }
+    rc = mox_find_ranges(e, (const uint8_t*)bytes.data(), offs.data(), prefixes.size(), MOX_FIND_PREFIX, p_first.data(), p_last.data(),
+                         p_sums.data(), nullptr);
+    for (size_t i = 0; i < prefixes.size() && rc == MOX_OK; i++) rc = mox_top_rows(e, p_first[i], p_last[i] - p_first[i], 10, &p_top[i]);
+  }
   if (rc == MOX_OK && by_count) rc = mox_rank_result(e, 0, nullptr);
   if (rc == MOX_OK) rc = mox_write_result(e, out.c_str());
   if (rc == MOX_OK) rc = mox_top_words(e, 10, &t);
@@ -130,7 +154,17 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < words.size(); i++) printf("%s: %llu\n", words[i].c_str(), (unsigned long long)counts[i]);
     }
   }
+  for (size_t i = 0; i < prefixes.size() && rc == MOX_OK; i++) {
+    printf("Prefix %s: %llu words, %llu tokens\n", prefixes[i].c_str(), (unsigned long long)(p_last[i] - p_first[i]),
+           (unsigned long long)p_sums[i]);
+    const mox_table* pt = p_top[i];
+    for (uint64_t j = 0; j < pt->n; j++) {
+      fwrite(pt->bytes + pt->offs[j], 1, pt->offs[j + 1] - pt->offs[j], stdout);
+      printf(": %llu\n", (unsigned long long)pt->counts[j]);
+    }
+  }
   if (rc != MOX_OK) fprintf(stderr, "Error: %s\n", mox_last_error());
+  for (mox_table* pt : p_top) mox_table_free(pt);
   mox_table_free(t);
   mox_engine_destroy(e);
   return rc == MOX_OK ? 0 : 1;

@@ -1001,6 +1001,22 @@ int run_file_overlapped(mox_engine* e, int fd, size_t len) {
   return MOX_OK;
 }
 
+// MOX_F_SORT_BYTES before a fetch: bytewise order on the GPU (mox_bsort.hip),
+// unless the result is sorted already or was ranked (an explicit ranking wins
+// over the flag).  *host_sort: the table is too big for the sort's device
+// scratch, so the fetched copy is to be sorted on the host.
+int sort_for_fetch(mox_engine* e, bool* host_sort) {
+  *host_sort = false;
+  if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted && !e->res.ranked) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = bsort_table(e);
+    if (rc == MOX_ENOMEM) *host_sort = true;
+    else if (rc) return rc;
+    e->stats.ms_sort = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return MOX_OK;
+}
+
 }  // namespace mox_host
 
 // ============================================================== C ABI
@@ -1051,6 +1067,7 @@ void mox_engine_destroy(mox_engine* e) {
   filter_free(e);
   rank_free(e);
   rekey_free(e);
+  find_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {
@@ -1167,22 +1184,6 @@ int mox_run_range(mox_engine* e, const void* d_buf, size_t buf_len, size_t own_b
 }
 
 int mox_run_device(mox_engine* e, const void* d_text, size_t len) { return mox_run_range(e, d_text, len, 0, len, 1); }
-
-// MOX_F_SORT_BYTES before a fetch: bytewise order on the GPU (mox_bsort.hip),
-// unless the result is sorted already or was ranked (an explicit ranking wins
-// over the flag).  *host_sort: the table is too big for the sort's device
-// scratch, so the fetched copy is to be sorted on the host.
-static int sort_for_fetch(mox_engine* e, bool* host_sort) {
-  *host_sort = false;
-  if ((e->flags & MOX_F_SORT_BYTES) && !e->res.sorted && !e->res.ranked) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = bsort_table(e);
-    if (rc == MOX_ENOMEM) *host_sort = true;
-    else if (rc) return rc;
-    e->stats.ms_sort = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return MOX_OK;
-}
 
 int mox_fetch_table(mox_engine* e, mox_table** out) {
   if (!e || !out) return fail(MOX_EINVAL, "NULL argument");

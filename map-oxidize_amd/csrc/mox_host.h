@@ -4,7 +4,8 @@
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
 // the device-resident accumulator (mox_accum.hip), the device lookup
 // (mox_lookup.hip), the device filter (mox_filter.hip), the device ranking
-// (mox_rank.hip) and the device re-keying (mox_rekey.hip).  The device-side
+// (mox_rank.hip), the device re-keying (mox_rekey.hip) and the device search
+// of the sorted result (mox_find.hip).  The device-side
 // helpers those kernels share are in mox_dev.h and mox_pack.h (the two
 // packers); the host-side ones (result_begin, table_reserve and the
 // declarations around it, Received: the hand-off to the reduce-only pass) are below.
@@ -210,6 +211,9 @@ struct mox_engine {
   // device re-keying (mox_rekey.hip): the packer's tile counts (the wire image
   // goes to x_recv_short / x_recv_blob)
   DevBuf q_tc;
+  // device search (mox_find.hip): scratch (outputs, keys, scanned tile sums), the
+  // pinned block the key offsets go up and the outputs come back through
+  DevBuf fd_tmp, fd_pin;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -283,6 +287,8 @@ int finish_pass(mox_engine* e, const Seq& q);
 int engine_create_one(const mox_config* cfg, int device, mox_engine** out);
 int stage_host_range(mox_engine* e, const uint8_t* text, size_t len);
 int stage_file_range(mox_engine* e, int fd, uint64_t off, size_t len);
+// MOX_F_SORT_BYTES before a fetch: the implicit device sort (mox_fetch_table, mox_fetch_rows, mox_find_ranges).
+int sort_for_fetch(mox_engine* e, bool* host_sort);
 // ---- mox_multi.hip
 int grow_dev(DevBuf& b, size_t bytes);
 int grow_pinned(DevBuf& b, size_t bytes);
@@ -339,4 +345,6 @@ void filter_free(mox_engine* e);
 void rank_free(mox_engine* e);
 // ---- mox_rekey.hip
 void rekey_free(mox_engine* e);
+// ---- mox_find.hip
+void find_free(mox_engine* e);
 }  // namespace mox_host

@@ -33,6 +33,9 @@
 //     long word) behind the counts and offsets, and one copy brings the block
 //     to the host.
 //
+// mox_top_rows is the same selection over a row range of the table: the host
+// passes the counts and offsets from the range's first row on (top_of_rows).
+//
 // Scratch is O(n / TK_TILE + k): the tile counts, and a fixed 200 KiB of
 // control block, histograms, candidates and outputs.  The result table itself
 // is only read.
@@ -306,13 +309,15 @@ void topk_free(mox_engine* e) {
 
 }  // namespace mox_host
 
-extern "C" int mox_top_words(mox_engine* e, size_t k, mox_table** out) {
-  if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
-  *out = nullptr;
-  if (k > MOX_TOP_MAX) return fail(MOX_EINVAL, "k = %zu (at most MOX_TOP_MAX = %d)", k, MOX_TOP_MAX);
-  if (int rc = result_begin(e)) return rc;
+// The top-k of n rows of the result (a result is open: result_begin): row i's
+// count is r_counts[i] and its word bytes[r_offs[i], r_offs[i + 1]) of the
+// result's bytes, so a row range of the table is the table's two arrays from
+// its first row on -- the kernels load counts as 8-byte words and offsets are
+// absolute.  Candidate indices, and with them the order of equal counts, are
+// relative to the range's first row, which is table order.
+static int top_of_rows(mox_engine* e, const uint64_t* r_counts, const uint64_t* r_offs, uint64_t n, size_t k, mox_table** out) {
   const mox_engine::Res& r = e->res;
-  const uint64_t n = r.n, kk = std::min<uint64_t>(k, n);
+  const uint64_t kk = std::min<uint64_t>(k, n);
   hipStream_t st = e->stream;
   const Seq q = seq_of(e);
   uint64_t nb = 0;
@@ -336,19 +341,19 @@ extern "C" int mox_top_words(mox_engine* e, size_t k, mox_table** out) {
     if (hgrid > 0x7FFFFFFFull) return fail(MOX_EINVAL, "top words: %llu words", (unsigned long long)n);
     const uint32_t wgrid = (uint32_t)std::min<uint64_t>((ntiles + TK_WAVES - 1) / TK_WAVES, 8ull * e->n_cu);
     for (int level = 0; level < TK_LEVELS; level++) {
-      hipLaunchKernelGGL(k_tk_hist, dim3((uint32_t)hgrid), dim3(TK_T), 0, st, r.counts, n, level, ctl, hist);
+      hipLaunchKernelGGL(k_tk_hist, dim3((uint32_t)hgrid), dim3(TK_T), 0, st, r_counts, n, level, ctl, hist);
       q.step("k_tk_hist");
       hipLaunchKernelGGL(k_tk_pick, dim3(1), dim3(TK_BINS), 0, st, level, kk, ctl, (const unsigned long long*)hist);
       q.step("k_tk_pick");
     }
-    hipLaunchKernelGGL(k_tk_ties, dim3(wgrid), dim3(TK_T), 0, st, r.counts, n, ntiles, ctl, tcnt, cand);
+    hipLaunchKernelGGL(k_tk_ties, dim3(wgrid), dim3(TK_T), 0, st, r_counts, n, ntiles, ctl, tcnt, cand);
     q.step("k_tk_ties");
     hipLaunchKernelGGL(k_tk_scan, dim3(1), dim3(1024), 0, st, tcnt, ntiles);
     q.step("k_tk_scan");
-    hipLaunchKernelGGL(k_tk_emit, dim3(wgrid), dim3(TK_T), 0, st, r.counts, n, ntiles, kk, (const TkCtl*)ctl, (const uint64_t*)tcnt,
+    hipLaunchKernelGGL(k_tk_emit, dim3(wgrid), dim3(TK_T), 0, st, r_counts, n, ntiles, kk, (const TkCtl*)ctl, (const uint64_t*)tcnt,
                        cand);
     q.step("k_tk_emit");
-    hipLaunchKernelGGL(k_tk_sort, dim3(1), dim3(1024), 0, st, (const TkCand*)cand, kk, r.offs, ctl, o_counts, o_src, o_offs);
+    hipLaunchKernelGGL(k_tk_sort, dim3(1), dim3(1024), 0, st, (const TkCand*)cand, kk, r_offs, ctl, o_counts, o_src, o_offs);
     q.step("k_tk_sort");
     HIPCHK(hipGetLastError());
     // the one round trip before the output is sized: the selected words' byte length
@@ -390,4 +395,23 @@ extern "C" int mox_top_words(mox_engine* e, size_t k, mox_table** out) {
   }
   *out = t;
   return MOX_OK;
+}
+
+static int top_args(mox_engine* e, size_t k, mox_table** out) {
+  if (!e || !out) return fail(MOX_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (k > MOX_TOP_MAX) return fail(MOX_EINVAL, "k = %zu (at most MOX_TOP_MAX = %d)", k, MOX_TOP_MAX);
+  return result_begin(e);
+}
+
+extern "C" int mox_top_words(mox_engine* e, size_t k, mox_table** out) {
+  if (int rc = top_args(e, k, out)) return rc;
+  return top_of_rows(e, e->res.counts, e->res.offs, e->res.n, k, out);
+}
+
+extern "C" int mox_top_rows(mox_engine* e, uint64_t first, uint64_t n, size_t k, mox_table** out) {
+  if (int rc = top_args(e, k, out)) return rc;
+  const mox_engine::Res& r = e->res;
+  const uint64_t lo = std::min(first, r.n), cnt = std::min(n, r.n - lo);
+  return top_of_rows(e, r.counts + lo, r.offs + lo, cnt, k, out);
 }

@@ -46,6 +46,11 @@ RANK_MAX_WORDS = (1 << 32) - 1  # MOX_RANK_MAX_WORDS: the most words Engine.rank
 REKEY_TRIM_ASCII_PUNCT = 0x1  # MOX_REKEY_TRIM_ASCII_PUNCT: Engine.rekey_result strips ASCII punctuation
 # {MOX_REKEY_PUNCT_LO, MOX_REKEY_PUNCT_HI}: string.punctuation as a 128-bit set, bit (b & 63) of word b >> 6
 ASCII_PUNCT = (0xFC00FFFE00000000, 0x78000001F8000001)
+FIND_EXACT = 0   # MOX_FIND_EXACT: Engine.find gives the row whose word equals the key
+FIND_PREFIX = 1  # MOX_FIND_PREFIX: the rows whose word starts with the key
+FIND_LOWER = 2   # MOX_FIND_LOWER: first = last = the number of rows bytewise below the key
+FIND_MAX = 1 << 20  # MOX_FIND_MAX: the most keys one Engine.find call takes
+_FIND_MODES = {"exact": FIND_EXACT, "prefix": FIND_PREFIX, "lower": FIND_LOWER}
 
 
 class MoxError(RuntimeError):
@@ -187,6 +192,19 @@ class RekeyInfo(ctypes.Structure):
     ]
 
 
+class FindInfo(ctypes.Structure):
+    """mox_find_info: keys, keys with a non-empty range, rows in all ranges, whether the tile pass ran, device bytes, ms."""
+    _fields_ = [
+        ("queries", ctypes.c_uint64),
+        ("matched", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("tile_pass", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
 class _Table(ctypes.Structure):
     _fields_ = [
         ("n", ctypes.c_uint64),
@@ -295,6 +313,8 @@ def lib(path=None):
             "mox_rank_result": ([VP, ctypes.c_uint32, P(RankInfo)], I),
             "mox_fetch_rows": ([VP, U64, U64, P(P(_Table))], I),
             "mox_rekey_result": ([VP, P(Rekey), P(RekeyInfo)], I),
+            "mox_find_ranges": ([VP, VP, P(U64), U64, ctypes.c_uint32, P(U64), P(U64), P(U64), P(FindInfo)], I),
+            "mox_top_rows": ([VP, U64, U64, sz, P(P(_Table))], I),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -670,6 +690,70 @@ class Engine:
         info = RekeyInfo()
         self._c(self._L.mox_rekey_result(self._h, ctypes.byref(k), ctypes.byref(info)))
         return {f: (float(info.ms) if f == "ms" else int(getattr(info, f))) for f, _ in info._fields_ if f != "reserved"}
+
+    # -- row ranges in the sorted result (mox_find_ranges), and the top-k of a row range (mox_top_rows)
+    def find(self, keys, mode="prefix", with_sums=True, with_info=False):
+        """Row ranges of ``keys`` (an iterable of bytes; str is encoded as UTF-8) in
+        the bytewise-sorted device-resident result, by binary search on the GPU
+        (mox_find_ranges; at most FIND_MAX keys, taken verbatim).  ``mode``:
+        "exact" (the row whose word equals the key), "prefix" (the rows whose word
+        starts with it; b"" is every row) or "lower" (first = last = the rows below
+        the key), or a FIND_* constant.  Returns (first, last[, sums][, info]) as
+        numpy uint64 arrays: rows [first[i], last[i]) are what fetch_rows(first[i],
+        last[i] - first[i]) returns, an absent key gives first == last == its
+        insertion point, sums[i] is the wrapping sum of the range's counts; info is
+        the dict {"queries", "matched", "rows", "tile_pass", "device_bytes", "ms"}.
+        The result must be sorted (sort_result(); MOX_ESTATE otherwise)."""
+        from . import spill
+
+        ks = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in keys]
+        data, offs, _ = spill.pack_pairs(ks, [])
+        return self.find_packed(data, offs, mode, with_sums, with_info)
+
+    def find_packed(self, data, offs, mode="prefix", with_sums=True, with_info=False):
+        """find() over keys already packed: key i is data[offs[i]:offs[i+1]]
+        (data: bytes or a numpy uint8 array, offs: uint64[n + 1])."""
+        import numpy as np
+
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.size - 1
+        if n < 0:
+            raise ValueError("offs needs n + 1 entries")
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        if n and int(offs[-1]) > buf.size:
+            raise ValueError("offsets run past the keys' bytes")
+        first = np.zeros(n, dtype=np.uint64)
+        last = np.zeros(n, dtype=np.uint64)
+        sums = np.zeros(n, dtype=np.uint64) if with_sums else None
+        info = FindInfo()
+        U64P = ctypes.POINTER(ctypes.c_uint64)
+        self._c(self._L.mox_find_ranges(
+            self._h, ctypes.c_void_p(buf.ctypes.data if buf.size else None), offs.ctypes.data_as(U64P), n,
+            _FIND_MODES.get(mode, mode), first.ctypes.data_as(U64P), last.ctypes.data_as(U64P),
+            sums.ctypes.data_as(U64P) if with_sums else None, ctypes.byref(info)))
+        out = (first, last)
+        if with_sums:
+            out += (sums,)
+        if with_info:
+            out += ({k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"},)
+        return out
+
+    def top_rows(self, first, n, k=10):
+        """top_words(k) over rows [first, first + n) of the device-resident result:
+        count descending, ties in table order, tokens the whole result's; works on
+        any result, sorted or not (mox_top_rows; k <= TOP_MAX)."""
+        t = ctypes.POINTER(_Table)()
+        self._c(self._L.mox_top_rows(self._h, first, n, k, ctypes.byref(t)))
+        return Table(t, self._L)
+
+    def complete(self, prefix, k=10):
+        """The k most frequent words of the sorted device-resident result that start
+        with ``prefix``, as a Table: find(mode="prefix") + top_rows, no row outside
+        the prefix is touched.  Raises what find raises on an unsorted result; it
+        does not sort behind the caller's back."""
+        first, last = self.find([prefix], "prefix", with_sums=False)
+        return self.top_rows(int(first[0]), int(last[0] - first[0]), k)
 
     def stats(self):
         s = Stats()

@@ -111,6 +111,31 @@ def sum_lookups(parts, found=None):
     return total
 
 
+def sum_finds(per_rank):
+    """Global (rows, sums) from per-rank finds: ``per_rank[r]`` is rank r's
+    ``Engine.find(keys, mode)`` -- (first, last) or (first, last, sums) -- of the
+    same keys after a ranged exchange.  Each rank then owns a byte range of the
+    words, so the ranks' ``last - first`` and ``sums`` add up (sums wrapping, as on
+    the device) to what a gather followed by one find gives, without gathering.
+    Returns two numpy uint64 arrays; sums is None when a rank's tuple has none.
+    ValueError when the lengths differ."""
+    import numpy as np
+
+    parts = [tuple(np.asarray(a, dtype=np.uint64).reshape(-1) for a in p[:3]) for p in per_rank]
+    if not parts:
+        return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+    n = parts[0][0].size
+    if any(a.size != n for p in parts for a in p):
+        raise ValueError("per-rank finds differ in length")
+    rows = np.zeros(n, dtype=np.uint64)
+    sums = np.zeros(n, dtype=np.uint64) if all(len(p) == 3 for p in parts) else None
+    for p in parts:
+        rows += p[1] - p[0]
+        if sums is not None:
+            sums += p[2]
+    return rows, sums
+
+
 class ThreadAlltoall:
     """In-process all-to-all between ``world`` threads (one engine per thread),
     for exercising the exchange with several ranks on one GPU without a process
