@@ -15,7 +15,7 @@ all: $(OUT)/libmox.so $(OUT)/libmox_corpus.so $(OUT)/meduce-gpu $(OUT)/libmox_ch
 $(OUT)/mox_kernels.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSRC)/mox_internal.h Makefile
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
-HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_dev.h $(CSRC)/mox_pack.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
+HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_dev.h $(CSRC)/mox_pack.h $(CSRC)/mox_wordhash.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
 $(OUT)/mox_engine.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -51,10 +51,13 @@ $(OUT)/mox_rekey.o: $(CSRC)/mox_rekey.hip $(HOST_DEPS)
 $(OUT)/mox_find.o: $(CSRC)/mox_find.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
+$(OUT)/mox_join.o: $(CSRC)/mox_join.hip $(HOST_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
+
 $(OUT)/mox_table.o: $(CSRC)/mox_table.cpp $(CSRC)/mox_table.h
 	g++ -O3 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
 
-$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_table.o
+$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_join.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # check build: device bounds checks on every derived index (MOX_CHK, mox_internal.h);
@@ -65,7 +68,7 @@ $(OUT)/mox_kernels_check.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSR
 $(OUT)/mox_engine_check.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
 	$(HIPCC) $(HIPFLAGS) -DMOX_CHECK -c $< -o $@
 
-$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_table.o
+$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_join.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 check: $(OUT)/libmox_check.so
@@ -96,8 +99,12 @@ $(OUT)/mox_lookup_hc.o: $(CSRC)/mox_lookup.hip $(HOST_DEPS)
 $(OUT)/mox_rekey_hc.o: $(CSRC)/mox_rekey.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) $(HC_FLAGS) -c $< -o $@
 
+# (the join hashes every word of both tables: fnv_finish must truncate there too)
+$(OUT)/mox_join_hc.o: $(CSRC)/mox_join.hip $(HOST_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) $(HC_FLAGS) -c $< -o $@
+
 # (the filter hashes nothing itself: its list term goes through the _hc lookup, so the plain object serves)
-$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum_hc.o $(OUT)/mox_lookup_hc.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey_hc.o $(OUT)/mox_find.o $(OUT)/mox_table.o
+$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum_hc.o $(OUT)/mox_lookup_hc.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey_hc.o $(OUT)/mox_find.o $(OUT)/mox_join_hc.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 hc: $(OUT)/libmox_hc.so

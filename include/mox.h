@@ -467,6 +467,86 @@ typedef struct mox_filter_info {
 } mox_filter_info;
 int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_info* info /* may be NULL */);
 
+/* ---- joining the device-resident result against the accumulated total ---- */
+/* Matches the device-resident result R against the accumulator's total T
+ * (mox_accumulate), on the GPU, and keeps the rows of R the mode selects:
+ * MOX_JOIN_SEMI the rows whose word T holds ("known words"), MOX_JOIN_ANTI the
+ * rows whose word T lacks ("new words": the window minus the total's
+ * vocabulary).  Neither table is fetched and no host pass runs over them; one
+ * 64-byte block comes back.  *info also carries the overlap sums two corpora
+ * are compared by: words_matched (vocabulary overlap), the tokens on shared
+ * words on either side, and tokens_min = sum of min(a, b), the multiset
+ * intersection that weighted Jaccard needs.
+ * Operands: R is the result in any form: a run's, mox_reduce_pairs, exchanged,
+ * gathered, mox_run_shards, sorted, ranked, filtered, re-keyed, joined, or a
+ * total that is itself the result.  T is the accumulator's total.  An empty
+ * accumulator (no fold since create or mox_accumulate_reset) is an empty T:
+ * SEMI keeps nothing, ANTI keeps everything, no kernel reads T and the call is
+ * not an error; an accumulator that holds an empty table behaves the same.
+ * Matching: words match verbatim and bytewise, and the length is part of the
+ * word ("ab" is not "ab\0").  A word T holds with count 0 is held: SEMI keeps
+ * it, and MOX_JOIN_COUNTS_TOTAL gives it 0.
+ * Counts: kept rows keep their own count (MOX_JOIN_COUNTS_RESULT), take T's
+ * (MOX_JOIN_COUNTS_TOTAL: "seen before, and how often overall") or the smaller
+ * of the two (MOX_JOIN_COUNTS_MIN); the last two with SEMI only.
+ * The new result: the kept rows in the order they had in R; tokens = the sum
+ * of the kept counts as written, substituted ones included, wrapping as
+ * uint64_t.  Sorted and folded state are R's.  Ranked state is R's with
+ * MOX_JOIN_COUNTS_RESULT; with _TOTAL or _MIN it is cleared, unless at most one
+ * row is kept.  As after a filter the new result is no pass's table and no
+ * exchanged one: mox_exchange / mox_gather afterwards return MOX_ESTATE.  It
+ * lives where a filtered result lives, so joining or filtering it again works.
+ * The accumulator is untouched in every case.  The call never sorts,
+ * MOX_F_SORT_BYTES or not.
+ * MOX_JOIN_COUNT_ONLY: only *info is produced; the result, its flags and its
+ * buffers are exactly what they were.
+ * Completes pending asynchronous passes first.  An engine group: member 0's
+ * gathered result against member 0's accumulator, on member 0.
+ * Distributed use: after a hash-owner mox_exchange (no MOX_F_SORT_BYTES) a
+ * word's owner rank is the same in every window, so ranks that accumulate
+ * their exchanged results join locally and add their infos
+ * (mox.dist.sum_joins).  With ranged owners (MOX_F_SORT_BYTES) the splitters
+ * move from exchange to exchange and a local join is wrong: gather first.
+ * info may be NULL.  Device memory: a hash set over R of 32 to 64 bytes per row
+ * of R (8-byte slots, the power of two >= 4 rows, load <= 1/4), 8 or 16 bytes
+ * per row of R for the matched counts, and the filter's scratch and output
+ * buffers; nothing is sized by T.  Held by the engine until mox_engine_destroy.
+ * MOX_ESTATE: no result yet.  MOX_EINVAL: a NULL engine or spec, an unknown
+ * mode, counts value or flag, ANTI with a counts value other than
+ * MOX_JOIN_COUNTS_RESULT, a pad or reserved word that is not 0, a result of more
+ * than MOX_JOIN_MAX_WORDS rows.  MOX_ENOMEM: the scratch or the output buffers
+ * cannot be allocated.  After any error the result is exactly what it was and
+ * *info is untouched.
+ * MOX_JOIN_GRID=<workgroups> (tests; read at each call) caps every grid of the
+ * call; MOX_TEST_FAIL_JOIN=1 (tests; read at each call) returns MOX_ENOMEM
+ * after the stream pass and before any output buffer is written. */
+#define MOX_JOIN_SEMI 0u          /* keep the result's rows whose word the total holds */
+#define MOX_JOIN_ANTI 1u          /* keep the result's rows whose word the total lacks */
+#define MOX_JOIN_COUNTS_RESULT 0u /* kept rows keep their own count */
+#define MOX_JOIN_COUNTS_TOTAL  1u /* kept rows take the total's count        (SEMI only) */
+#define MOX_JOIN_COUNTS_MIN    2u /* kept rows take min(own, total's) count  (SEMI only) */
+#define MOX_JOIN_COUNT_ONLY 0x1u  /* flags: fill info, leave the result as it is */
+#define MOX_JOIN_MAX_WORDS 0xFFFFFFFEull  /* rows of the RESULT: a slot holds row + 1 in 32 bits */
+typedef struct mox_join {
+  uint32_t mode, counts, flags, pad;   /* pad must be 0 */
+  uint64_t reserved[4];                /* must be 0 */
+} mox_join;                            /* 48 bytes */
+typedef struct mox_join_info {
+  uint64_t words_in, words_total;      /* rows of the result / of the total */
+  uint64_t words_matched;              /* result words the total holds (whatever the mode) */
+  uint64_t words_kept;
+  uint64_t tokens_in, tokens_total;
+  uint64_t tokens_matched_result;      /* sum of the result's counts over matched words */
+  uint64_t tokens_matched_total;       /* sum of the total's counts over matched words */
+  uint64_t tokens_min;                 /* sum of min(result's, total's) over matched words */
+  uint64_t tokens_kept, bytes_kept;
+  uint64_t tag_mismatch;               /* probes with an equal tag and different bytes */
+  uint64_t device_bytes;
+  double ms;
+  uint64_t reserved[4];
+} mox_join_info;
+int mox_join_total(mox_engine* e, const mox_join* j, mox_join_info* info /* may be NULL */);
+
 /* ---- ranking the device-resident result by count, fetching it by rows ---- */
 /* Reorders the device-resident result by count, on the GPU: the same words
  * and counts, most frequent first, or least frequent first with

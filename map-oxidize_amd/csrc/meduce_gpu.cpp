@@ -42,6 +42,16 @@
 // those rows alone (mox_top_rows).  The queries run after that sort and before
 // any --by-count ranking.  P is taken verbatim, as --word's W.  Without the
 // option every output is what it always was.
+// --not-in BASE keeps only the input's words that the file BASE lacks (the new
+// words), --also-in BASE only those BASE holds too, each with the input's own
+// count (mox_join_total): BASE is counted into the device-resident accumulator
+// first, re-keyed first when --trim-punct is given, then the single input file
+// is counted and joined against that total on the device, after --trim-punct
+// and before --min-count, --stop and --by-count apply.  The tool's own
+// multi-file total uses the accumulator, so more than one input file, or
+// --chunk, together with either option is a usage error, and so are both
+// options together: exit status 2.  Without the options every output is what
+// it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
@@ -60,7 +70,8 @@ int main(int argc, char** argv) {
   unsigned long long chunk = 0;
   std::vector<std::string> words, prefixes;
   unsigned long long min_count = 0;
-  std::string stop_path;
+  std::string stop_path, base_path;
+  int n_not_in = 0, n_also_in = 0;
   bool have_stop = false, by_count = false, trim_punct = false;
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
@@ -70,11 +81,20 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--prefix") && i + 1 < argc) prefixes.push_back(argv[++i]);
     else if (!strcmp(argv[i], "--min-count") && i + 1 < argc) min_count = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--stop") && i + 1 < argc) { stop_path = argv[++i]; have_stop = true; }
+    else if (!strcmp(argv[i], "--not-in") && i + 1 < argc) { base_path = argv[++i]; n_not_in++; }
+    else if (!strcmp(argv[i], "--also-in") && i + 1 < argc) { base_path = argv[++i]; n_also_in++; }
     else if (!strcmp(argv[i], "--by-count")) by_count = true;
     else if (!strcmp(argv[i], "--trim-punct")) trim_punct = true;
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) paths.push_back("shakes.txt");
+  const bool join = n_not_in || n_also_in;
+  if (n_not_in && n_also_in) { fprintf(stderr, "Usage: --not-in and --also-in exclude each other\n"); return 2; }
+  if (n_not_in + n_also_in > 1) { fprintf(stderr, "Usage: one --not-in or --also-in\n"); return 2; }
+  if (join && (paths.size() > 1 || chunk)) {
+    fprintf(stderr, "Usage: --not-in / --also-in take one input file and no --chunk (the accumulator holds BASE)\n");
+    return 2;
+  }
   // the stop list: the file's words, split at ASCII whitespace
   std::string stop_bytes;
   std::vector<uint64_t> stop_offs(1, 0);
@@ -101,16 +121,25 @@ int main(int argc, char** argv) {
   if (mox_engine_create(&cfg, &e) != MOX_OK) { fprintf(stderr, "Error: %s\n", mox_last_error()); return 1; }
   mox_table* t = nullptr;
   int rc = MOX_OK;
+  mox_rekey rk;
+  memset(&rk, 0, sizeof rk);
+  rk.flags = MOX_REKEY_TRIM_ASCII_PUNCT;
+  if (join) {  // BASE becomes the accumulator's total
+    rc = mox_run_file(e, base_path.c_str());
+    if (rc == MOX_OK && trim_punct) rc = mox_rekey_result(e, &rk, nullptr);
+    if (rc == MOX_OK) rc = mox_accumulate(e);
+  }
   if (paths.size() == 1 && !chunk) {
-    rc = mox_run_file(e, paths[0].c_str());
+    if (rc == MOX_OK) rc = mox_run_file(e, paths[0].c_str());
   } else {
     for (size_t i = 0; i < paths.size() && rc == MOX_OK; i++) rc = mox_accumulate_file(e, paths[i].c_str(), chunk);
   }
-  if (rc == MOX_OK && trim_punct) {
-    mox_rekey k;
-    memset(&k, 0, sizeof k);
-    k.flags = MOX_REKEY_TRIM_ASCII_PUNCT;
-    rc = mox_rekey_result(e, &k, nullptr);
+  if (rc == MOX_OK && trim_punct) rc = mox_rekey_result(e, &rk, nullptr);
+  if (rc == MOX_OK && join) {
+    mox_join j;
+    memset(&j, 0, sizeof j);
+    j.mode = n_not_in ? MOX_JOIN_ANTI : MOX_JOIN_SEMI;
+    rc = mox_join_total(e, &j, nullptr);
   }
   if (rc == MOX_OK && (min_count || have_stop)) {
     mox_filter f;

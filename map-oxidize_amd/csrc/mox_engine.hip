@@ -1068,6 +1068,7 @@ void mox_engine_destroy(mox_engine* e) {
   rank_free(e);
   rekey_free(e);
   find_free(e);
+  join_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

@@ -51,6 +51,10 @@
 // e->res is repointed only when everything has succeeded.  Scratch (f_tmp) is
 // O(n / 8): three tile arrays, the keep mask and the list bitmap.
 //
+// The device join (mox_join_total, at the end of this file) runs the same
+// count, scan and emit passes: its match bitmap (mox_join.hip) is the list
+// bitmap, and FlTab::counts may point at substituted counts.
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   k_fl_mark   12 VGPRs, 26 SGPRs,     4 B LDS, no scratch, no spills (8 waves / SIMD)
 //   k_fl_count  43 VGPRs, 90 SGPRs,    96 B LDS, no scratch, no spills (8 waves / SIMD)
@@ -311,6 +315,74 @@ void filter_free(mox_engine* e) {
 
 }  // namespace mox_host
 
+namespace {
+
+// A call's scratch in f_tmp: [tile arrays 3 nt | totals 3 | list_found | pad 4] [keep masks 16 nt] [list bitmap]
+struct FlTmp {
+  uint64_t* tc;
+  uint64_t* keep;
+  uint32_t* listed;
+};
+
+// f_tmp grown and laid out for the table T, the totals and (with bitmap) the list bitmap zeroed.
+int fl_scratch(mox_engine* e, const FlTab& T, bool bitmap, FlTmp* s) {
+  const size_t tc_b = (3 * T.nt + 8) * 8, keep_b = T.nt * FL_STEPS * 8, bm_b = bitmap ? ((T.n + 63) / 64) * 8 + 8 : 0;
+  if (int rc = grow_dev(e->f_tmp, tc_b + keep_b + bm_b)) return rc;
+  s->tc = (uint64_t*)e->f_tmp.p;
+  s->keep = (uint64_t*)((uint8_t*)e->f_tmp.p + tc_b);
+  s->listed = (uint32_t*)((uint8_t*)e->f_tmp.p + tc_b + keep_b);
+  if (T.n) {
+    HIPCHK(hipMemsetAsync(s->tc + 3 * T.nt, 0, 64, e->stream));
+    if (bitmap) HIPCHK(hipMemsetAsync(s->listed, 0, bm_b, e->stream));
+  }
+  return MOX_OK;
+}
+
+// The count pass and the scan over a table with rows; tot[0, 4) = kept rows,
+// kept bytes, kept count sum, list words found.  Synchronises.
+int fl_select(mox_engine* e, const FlTab& T, const FlPred& P, const FlTmp& s, uint32_t grid, uint64_t* tot) {
+  hipStream_t st = e->stream;
+  const Seq q = seq_of(e);
+  hipLaunchKernelGGL(k_fl_count, dim3(grid), dim3(FL_T), 0, st, T, P, s.keep, s.tc);
+  q.step("k_fl_count");
+  hipLaunchKernelGGL(k_fl_scan, dim3(1), dim3(1024), 0, st, s.tc, T.nt);
+  q.step("k_fl_scan");
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(tot, s.tc + 3 * T.nt, 32, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return MOX_OK;
+}
+
+// The kept rows of T (tot: fl_select's) into the set of f_tab the result r does
+// not live in: *dst.  Synchronises; e->res is the caller's to repoint.
+int fl_emit(mox_engine* e, const mox_engine::Res& r, const FlTab& T, const FlTmp& s, uint32_t grid, const uint64_t* tot, DevBuf** dst_out) {
+  hipStream_t st = e->stream;
+  const Seq q = seq_of(e);
+  DevBuf* dst = table_other_set(e->f_tab, r);
+  if (int rc = table_reserve(dst[0], dst[1], dst[2], tot[0], tot[1])) return rc;
+  const FlOut out{(uint64_t*)dst[0].p, (uint64_t*)dst[1].p, (uint8_t*)dst[2].p, tot[0], tot[1]};
+  if (T.n) {
+    hipLaunchKernelGGL(k_fl_emit, dim3(grid), dim3(FL_T), 0, st, T, s.keep, s.tc, out);
+    q.step("k_fl_emit");
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(hipMemsetAsync(out.offs, 0, 8, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  *dst_out = dst;
+  return MOX_OK;
+}
+
+// device memory the filter (and the join, which shares it) holds
+uint64_t fl_device_bytes(const mox_engine* e) {
+  uint64_t b = e->f_tmp.cap;
+  for (auto& set : e->f_tab)
+    for (const DevBuf& d : set) b += d.cap;
+  return b;
+}
+
+}  // namespace
+
 extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_info* info) {
   if (!e) return fail(MOX_EINVAL, "engine is NULL");
   if (!f) return fail(MOX_EINVAL, "filter is NULL");
@@ -355,32 +427,20 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   }
   P.list_mode = f->words_mode == MOX_FILTER_WORDS_KEEP ? 2u : nq ? 1u : 0u;
 
-  // scratch: [tile arrays 3 nt | totals 3 | list_found | pad 4] [keep masks 16 nt] [list bitmap]
   const FlTab T{r.counts, r.offs, r.bytes, r.n, (r.n + FL_TILE - 1) / FL_TILE};
-  const size_t tc_b = (3 * T.nt + 8) * 8, keep_b = T.nt * FL_STEPS * 8, bm_b = P.list_mode ? ((r.n + 63) / 64) * 8 + 8 : 0;
-  if ((rc = grow_dev(e->f_tmp, tc_b + keep_b + bm_b))) return rc;
-  uint64_t* tc = (uint64_t*)e->f_tmp.p;
-  uint64_t* keep = (uint64_t*)((uint8_t*)e->f_tmp.p + tc_b);
-  uint32_t* listed = (uint32_t*)((uint8_t*)e->f_tmp.p + tc_b + keep_b);
-  P.listed = listed;
+  FlTmp s;
+  if ((rc = fl_scratch(e, T, P.list_mode != 0, &s))) return rc;
+  P.listed = s.listed;
   uint64_t* tot = e->h_tot;  // kept rows, kept bytes, kept count sum, list words found
   for (int k = 0; k < 4; k++) tot[k] = 0;
   const uint32_t grid = (uint32_t)std::min(T.nt, grid_cap(e, "MOX_FILTER_GRID"));
   if (T.n) {
-    HIPCHK(hipMemsetAsync(tc + 3 * T.nt, 0, 64, st));
-    if (P.list_mode) HIPCHK(hipMemsetAsync(listed, 0, bm_b, st));
     if (nq) {
       hipLaunchKernelGGL(k_fl_mark, dim3((uint32_t)std::min<uint64_t>((nq + FL_T - 1) / FL_T, 8ull * (uint64_t)e->n_cu)), dim3(FL_T), 0, st,
-                         d_index, nq, listed, T.n, (unsigned long long*)(tc + 3 * T.nt + 3));
+                         d_index, nq, s.listed, T.n, (unsigned long long*)(s.tc + 3 * T.nt + 3));
       q.step("k_fl_mark");
     }
-    hipLaunchKernelGGL(k_fl_count, dim3(grid), dim3(FL_T), 0, st, T, P, keep, tc);
-    q.step("k_fl_count");
-    hipLaunchKernelGGL(k_fl_scan, dim3(1), dim3(1024), 0, st, tc, T.nt);
-    q.step("k_fl_scan");
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(tot, tc + 3 * T.nt, 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = fl_select(e, T, P, s, grid, tot))) return rc;
   }
   if (tot[0] > r.n || tot[1] > r.nb || tot[3] > nq)
     return fail(MOX_EHIP, "filter: inconsistent totals (%llu of %llu rows, %llu of %llu bytes, %llu of %llu list words)",
@@ -394,9 +454,7 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   fi.bytes_kept = tot[1];
   fi.list_found = tot[3];
   auto finish = [&]() {
-    fi.device_bytes = e->f_tmp.cap;
-    for (auto& set : e->f_tab)
-      for (DevBuf& b : set) fi.device_bytes += b.cap;
+    fi.device_bytes = fl_device_bytes(e);
     fi.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (info) *info = fi;
     return MOX_OK;
@@ -404,21 +462,91 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   if (f->flags & MOX_FILTER_COUNT_ONLY) return finish();
   if (test_fail_hook("MOX_TEST_FAIL_FILTER"))
     return fail(MOX_ENOMEM, "filter: injected failure before the output is written (MOX_TEST_FAIL_FILTER)");
-  DevBuf* dst = table_other_set(e->f_tab, r);
-  if ((rc = table_reserve(dst[0], dst[1], dst[2], tot[0], tot[1]))) return rc;
-  const FlOut out{(uint64_t*)dst[0].p, (uint64_t*)dst[1].p, (uint8_t*)dst[2].p, tot[0], tot[1]};
-  if (T.n) {
-    hipLaunchKernelGGL(k_fl_emit, dim3(grid), dim3(FL_T), 0, st, T, keep, tc, out);
-    q.step("k_fl_emit");
-    HIPCHK(hipGetLastError());
-  } else {
-    HIPCHK(hipMemsetAsync(out.offs, 0, 8, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
+  DevBuf* dst;
+  if ((rc = fl_emit(e, r, T, s, grid, tot, &dst))) return rc;
   // the kept words are the result: order, sorted and folded as the source had them
   mox_engine::Res& res = e->res;
   res_point_at(res, dst, tot[0], tot[1], tot[2]);
   res.pass = false;
   res.exchanged = false;
+  return finish();
+}
+
+// The join's host side lives here, beside the compaction it shares with the
+// filter; its kernels and the match are mox_join.hip's (join_match).
+extern "C" int mox_join_total(mox_engine* e, const mox_join* j, mox_join_info* info) {
+  if (!e) return fail(MOX_EINVAL, "engine is NULL");
+  if (!j) return fail(MOX_EINVAL, "join is NULL");
+  for (uint64_t r : j->reserved)
+    if (r) return fail(MOX_EINVAL, "join: a reserved word is not 0");
+  if (j->pad) return fail(MOX_EINVAL, "join: pad is not 0");
+  if (j->flags & ~MOX_JOIN_COUNT_ONLY) return fail(MOX_EINVAL, "join: unknown flags 0x%x", j->flags);
+  if (j->mode != MOX_JOIN_SEMI && j->mode != MOX_JOIN_ANTI) return fail(MOX_EINVAL, "join: unknown mode %u", j->mode);
+  if (j->counts != MOX_JOIN_COUNTS_RESULT && j->counts != MOX_JOIN_COUNTS_TOTAL && j->counts != MOX_JOIN_COUNTS_MIN)
+    return fail(MOX_EINVAL, "join: unknown counts value %u", j->counts);
+  if (j->mode == MOX_JOIN_ANTI && j->counts != MOX_JOIN_COUNTS_RESULT)
+    return fail(MOX_EINVAL, "join: MOX_JOIN_ANTI keeps words the total lacks: only MOX_JOIN_COUNTS_RESULT");
+  if (int rc = result_begin(e)) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  const mox_engine::Res r = e->res;
+  if (r.n > MOX_JOIN_MAX_WORDS)
+    return fail(MOX_EINVAL, "join: a result of %llu words (at most MOX_JOIN_MAX_WORDS = %llu)", (unsigned long long)r.n, MOX_JOIN_MAX_WORDS);
+  const uint64_t tn = e->acc.have ? e->acc.n : 0;  // an empty accumulator is an empty total
+  const uint64_t cap = grid_cap(e, "MOX_JOIN_GRID");
+  int rc;
+  FlTab T{r.counts, r.offs, r.bytes, r.n, (r.n + FL_TILE - 1) / FL_TILE};
+  FlTmp s;
+  if ((rc = fl_scratch(e, T, true, &s))) return rc;
+  // the match bitmap is the filter's list bitmap; with an empty side it stays zero and no kernel reads the total
+  JoinSums js;
+  const uint64_t* subst = nullptr;
+  if (r.n && tn &&
+      (rc = join_match(e, r, (const uint64_t*)e->a_tab[0].p, (const uint64_t*)e->a_tab[1].p, (const uint8_t*)e->a_tab[2].p, tn, j->counts,
+                       s.listed, cap, &js, &subst)))
+    return rc;
+  if (subst) T.counts = subst;  // the kept rows carry the total's count or the smaller one
+  FlPred P{};
+  P.max_count = ~0ull;
+  P.max_len = ~0ull;
+  P.listed = s.listed;
+  P.list_mode = j->mode == MOX_JOIN_SEMI ? 2u : 1u;
+  uint64_t* tot = e->h_tot;  // kept rows, kept bytes, kept count sum
+  for (int k = 0; k < 4; k++) tot[k] = 0;
+  const uint32_t grid = (uint32_t)std::min(T.nt, cap);
+  if (T.n && (rc = fl_select(e, T, P, s, grid, tot))) return rc;
+  const uint64_t want = j->mode == MOX_JOIN_SEMI ? js.matched : r.n - js.matched;
+  if (tot[0] != want || tot[1] > r.nb)
+    return fail(MOX_EHIP, "join: inconsistent totals (%llu rows kept, %llu of %llu matched, %llu of %llu bytes)", (unsigned long long)tot[0],
+                (unsigned long long)js.matched, (unsigned long long)r.n, (unsigned long long)tot[1], (unsigned long long)r.nb);
+  mox_join_info ji{};
+  ji.words_in = r.n;
+  ji.words_total = tn;
+  ji.words_matched = js.matched;
+  ji.words_kept = tot[0];
+  ji.tokens_in = r.tokens;
+  ji.tokens_total = e->acc.have ? e->acc.tokens : 0;
+  ji.tokens_matched_result = js.tokens_result;
+  ji.tokens_matched_total = js.tokens_total;
+  ji.tokens_min = js.tokens_min;
+  ji.tokens_kept = tot[2];
+  ji.bytes_kept = tot[1];
+  ji.tag_mismatch = js.tag_mismatch;
+  auto finish = [&]() {
+    ji.device_bytes = fl_device_bytes(e) + e->j_tmp.cap;
+    ji.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = ji;
+    return MOX_OK;
+  };
+  if (j->flags & MOX_JOIN_COUNT_ONLY) return finish();
+  if (test_fail_hook("MOX_TEST_FAIL_JOIN"))
+    return fail(MOX_ENOMEM, "join: injected failure before the output is written (MOX_TEST_FAIL_JOIN)");
+  DevBuf* dst;
+  if ((rc = fl_emit(e, r, T, s, grid, tot, &dst))) return rc;
+  // the kept rows are the result: order, sorted and folded as R had them; substituted counts are in no count order
+  mox_engine::Res& res = e->res;
+  res_point_at(res, dst, tot[0], tot[1], tot[2]);
+  res.pass = false;
+  res.exchanged = false;
+  if (j->counts != MOX_JOIN_COUNTS_RESULT && tot[0] > 1) res.ranked = false;
   return finish();
 }

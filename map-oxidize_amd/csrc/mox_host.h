@@ -4,8 +4,9 @@
 // device top-k (mox_topk.hip), the device text rendering (mox_text.hip) and
 // the device-resident accumulator (mox_accum.hip), the device lookup
 // (mox_lookup.hip), the device filter (mox_filter.hip), the device ranking
-// (mox_rank.hip), the device re-keying (mox_rekey.hip) and the device search
-// of the sorted result (mox_find.hip).  The device-side
+// (mox_rank.hip), the device re-keying (mox_rekey.hip), the device search
+// of the sorted result (mox_find.hip) and the device join against the total
+// (mox_join.hip).  The device-side
 // helpers those kernels share are in mox_dev.h and mox_pack.h (the two
 // packers); the host-side ones (result_begin, table_reserve and the
 // declarations around it, Received: the hand-off to the reduce-only pass) are below.
@@ -214,6 +215,10 @@ struct mox_engine {
   // device search (mox_find.hip): scratch (outputs, keys, scanned tile sums), the
   // pinned block the key offsets go up and the outputs come back through
   DevBuf fd_tmp, fd_pin;
+  // device join (mox_join.hip): scratch (control block, the hash set over the
+  // result's rows, matched and substituted counts); the match bitmap, the tile
+  // arrays and the output are the filter's (f_tmp, f_tab)
+  DevBuf j_tmp;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -347,4 +352,12 @@ void rank_free(mox_engine* e);
 void rekey_free(mox_engine* e);
 // ---- mox_find.hip
 void find_free(mox_engine* e);
+// ---- mox_join.hip
+void join_free(mox_engine* e);
+// Sums over the rows of the result whose word the other table holds.
+struct JoinSums {
+  uint64_t matched = 0, tokens_result = 0, tokens_total = 0, tokens_min = 0, tag_mismatch = 0;
+};
+int join_match(mox_engine* e, const mox_engine::Res& r, const uint64_t* t_counts, const uint64_t* t_offs, const uint8_t* t_bytes,
+               uint64_t t_n, uint32_t counts_mode, uint32_t* matched, uint64_t cap, JoinSums* sums, const uint64_t** subst);
 }  // namespace mox_host

@@ -41,6 +41,15 @@ FILTER_PREFIX_MAX = 16  # MOX_FILTER_PREFIX_MAX: the longest prefix Engine.filte
 FILTER_WORDS_DROP = 0   # MOX_FILTER_WORDS_DROP: listed words are removed (stop list)
 FILTER_WORDS_KEEP = 1   # MOX_FILTER_WORDS_KEEP: only listed words survive (vocabulary)
 FILTER_COUNT_ONLY = 0x1  # MOX_FILTER_COUNT_ONLY: fill the info, leave the result as it is
+JOIN_SEMI = 0  # MOX_JOIN_SEMI: Engine.join_total keeps the result's words the total holds
+JOIN_ANTI = 1  # MOX_JOIN_ANTI: ... the result's words the total lacks
+JOIN_COUNTS_RESULT = 0  # MOX_JOIN_COUNTS_RESULT: kept rows keep their own count
+JOIN_COUNTS_TOTAL = 1   # MOX_JOIN_COUNTS_TOTAL: kept rows take the total's count (semi only)
+JOIN_COUNTS_MIN = 2     # MOX_JOIN_COUNTS_MIN: kept rows take the smaller of both counts (semi only)
+JOIN_COUNT_ONLY = 0x1   # MOX_JOIN_COUNT_ONLY: fill the info, leave the result as it is
+JOIN_MAX_WORDS = 0xFFFFFFFE  # MOX_JOIN_MAX_WORDS: the most rows of the result Engine.join_total takes
+_JOIN_MODES = {"semi": JOIN_SEMI, "anti": JOIN_ANTI}
+_JOIN_COUNTS = {"result": JOIN_COUNTS_RESULT, "total": JOIN_COUNTS_TOTAL, "min": JOIN_COUNTS_MIN}
 RANK_ASCENDING = 0x1  # MOX_RANK_ASCENDING: Engine.rank_result orders least frequent first
 RANK_MAX_WORDS = (1 << 32) - 1  # MOX_RANK_MAX_WORDS: the most words Engine.rank_result takes
 REKEY_TRIM_ASCII_PUNCT = 0x1  # MOX_REKEY_TRIM_ASCII_PUNCT: Engine.rekey_result strips ASCII punctuation
@@ -145,6 +154,38 @@ class FilterInfo(ctypes.Structure):
         ("tokens_kept", ctypes.c_uint64),
         ("bytes_kept", ctypes.c_uint64),
         ("list_found", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class Join(ctypes.Structure):
+    """mox_join: the spec of mox_join_total."""
+    _fields_ = [
+        ("mode", ctypes.c_uint32),
+        ("counts", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class JoinInfo(ctypes.Structure):
+    """mox_join_info: rows and tokens of the result and of the total, matched and kept words, the overlap sums, device bytes, ms."""
+    _fields_ = [
+        ("words_in", ctypes.c_uint64),
+        ("words_total", ctypes.c_uint64),
+        ("words_matched", ctypes.c_uint64),
+        ("words_kept", ctypes.c_uint64),
+        ("tokens_in", ctypes.c_uint64),
+        ("tokens_total", ctypes.c_uint64),
+        ("tokens_matched_result", ctypes.c_uint64),
+        ("tokens_matched_total", ctypes.c_uint64),
+        ("tokens_min", ctypes.c_uint64),
+        ("tokens_kept", ctypes.c_uint64),
+        ("bytes_kept", ctypes.c_uint64),
+        ("tag_mismatch", ctypes.c_uint64),
         ("device_bytes", ctypes.c_uint64),
         ("ms", ctypes.c_double),
         ("reserved", ctypes.c_uint64 * 4),
@@ -310,6 +351,7 @@ def lib(path=None):
             "mox_accumulate_info": ([VP, P(AccumInfo)], I),
             "mox_lookup_words": ([VP, VP, P(U64), U64, P(U64), P(U64), P(LookupInfo)], I),
             "mox_filter_result": ([VP, P(Filter), P(FilterInfo)], I),
+            "mox_join_total": ([VP, P(Join), P(JoinInfo)], I),
             "mox_rank_result": ([VP, ctypes.c_uint32, P(RankInfo)], I),
             "mox_fetch_rows": ([VP, U64, U64, P(P(_Table))], I),
             "mox_rekey_result": ([VP, P(Rekey), P(RekeyInfo)], I),
@@ -650,6 +692,29 @@ class Engine:
             f.n_words = n
         info = FilterInfo()
         self._c(self._L.mox_filter_result(self._h, ctypes.byref(f), ctypes.byref(info)))
+        return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+
+    # -- the result joined against the accumulated total on the device (mox_join_total)
+    def join_total(self, mode="semi", counts="result", count_only=False):
+        """Keep the words of the device-resident result that the accumulator's
+        total holds (``mode`` "semi") or lacks ("anti": the new words); they
+        become the engine's result, in the order they had (mox_join_total).
+        ``counts``: kept words keep their own count ("result"), take the total's
+        ("total") or the smaller of both ("min"); the last two with "semi" only (with "anti": MOX_EINVAL).
+        count_only: nothing changes, only the info is produced.  An empty
+        accumulator is an empty total.  Returns the info dict {"words_in",
+        "words_total", "words_matched", "words_kept", "tokens_in", "tokens_total",
+        "tokens_matched_result", "tokens_matched_total", "tokens_min",
+        "tokens_kept", "bytes_kept", "tag_mismatch", "device_bytes", "ms"}."""
+        if mode not in _JOIN_MODES:
+            raise ValueError("mode %r: one of %s" % (mode, sorted(_JOIN_MODES)))
+        if counts not in _JOIN_COUNTS:
+            raise ValueError("counts %r: one of %s" % (counts, sorted(_JOIN_COUNTS)))
+        j = Join()
+        j.mode, j.counts = _JOIN_MODES[mode], _JOIN_COUNTS[counts]
+        j.flags = JOIN_COUNT_ONLY if count_only else 0
+        info = JoinInfo()
+        self._c(self._L.mox_join_total(self._h, ctypes.byref(j), ctypes.byref(info)))
         return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
 
     # -- the result ordered by count on the device (mox_rank_result), and read by rows

@@ -136,6 +136,25 @@ def sum_finds(per_rank):
     return rows, sums
 
 
+def sum_joins(infos):
+    """The global join info from per-rank joins: ``infos[r]`` is rank r's
+    ``Engine.join_total(...)`` after a hash-owner exchange (no MOX_F_SORT_BYTES),
+    where every rank accumulates its exchanged results: a word's owner is the
+    same rank in every window, so the ranks' words, tokens and overlap sums add up
+    (wrapping, as on the device) to what a gather followed by one join gives.
+    ``device_bytes`` and ``ms`` are not additive: the largest is reported.  With
+    ranged owners a local join is wrong: gather first."""
+    infos = list(infos)
+    out = {}
+    for info in infos:
+        for k, v in info.items():
+            if k in ("device_bytes", "ms"):
+                out[k] = max(out.get(k, v), v)
+            else:
+                out[k] = (out.get(k, 0) + v) & ((1 << 64) - 1)
+    return out
+
+
 class ThreadAlltoall:
     """In-process all-to-all between ``world`` threads (one engine per thread),
     for exercising the exchange with several ranks on one GPU without a process
