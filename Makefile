@@ -51,13 +51,17 @@ $(OUT)/mox_rekey.o: $(CSRC)/mox_rekey.hip $(HOST_DEPS)
 $(OUT)/mox_find.o: $(CSRC)/mox_find.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
+# (the histograms hash nothing: one object serves libmox.so, libmox_check.so and libmox_hc.so)
+$(OUT)/mox_hist.o: $(CSRC)/mox_hist.hip $(HOST_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
+
 $(OUT)/mox_join.o: $(CSRC)/mox_join.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) -c $< -o $@
 
 $(OUT)/mox_table.o: $(CSRC)/mox_table.cpp $(CSRC)/mox_table.h
 	g++ -O3 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
 
-$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_join.o $(OUT)/mox_table.o
+$(OUT)/libmox.so: $(OUT)/mox_kernels.o $(OUT)/mox_engine.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_hist.o $(OUT)/mox_join.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # check build: device bounds checks on every derived index (MOX_CHK, mox_internal.h);
@@ -68,7 +72,7 @@ $(OUT)/mox_kernels_check.o: $(CSRC)/mox_kernels.hip $(CSRC)/mox_reduce.inc $(CSR
 $(OUT)/mox_engine_check.o: $(CSRC)/mox_engine.hip $(HOST_DEPS) $(CSRC)/mox_unicode_tables.h
 	$(HIPCC) $(HIPFLAGS) -DMOX_CHECK -c $< -o $@
 
-$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_join.o $(OUT)/mox_table.o
+$(OUT)/libmox_check.so: $(OUT)/mox_kernels_check.o $(OUT)/mox_engine_check.o $(OUT)/mox_multi.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum.o $(OUT)/mox_lookup.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey.o $(OUT)/mox_find.o $(OUT)/mox_hist.o $(OUT)/mox_join.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 check: $(OUT)/libmox_check.so
@@ -104,7 +108,7 @@ $(OUT)/mox_join_hc.o: $(CSRC)/mox_join.hip $(HOST_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(KERNEL_FLAGS) $(HC_FLAGS) -c $< -o $@
 
 # (the filter hashes nothing itself: its list term goes through the _hc lookup, so the plain object serves)
-$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum_hc.o $(OUT)/mox_lookup_hc.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey_hc.o $(OUT)/mox_find.o $(OUT)/mox_join_hc.o $(OUT)/mox_table.o
+$(OUT)/libmox_hc.so: $(OUT)/mox_kernels_hc.o $(OUT)/mox_engine_hc.o $(OUT)/mox_multi_hc.o $(OUT)/mox_bsort.o $(OUT)/mox_topk.o $(OUT)/mox_text.o $(OUT)/mox_accum_hc.o $(OUT)/mox_lookup_hc.o $(OUT)/mox_filter.o $(OUT)/mox_rank.o $(OUT)/mox_rekey_hc.o $(OUT)/mox_find.o $(OUT)/mox_hist.o $(OUT)/mox_join_hc.o $(OUT)/mox_table.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 hc: $(OUT)/libmox_hc.so

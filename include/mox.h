@@ -786,6 +786,106 @@ int mox_find_ranges(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, u
  * k == 0: an empty table.  Errors as mox_top_words. */
 int mox_top_rows(mox_engine* e, uint64_t first, uint64_t n, size_t k, mox_table** out);
 
+/* ---- histograms of the device-resident result ---- */
+/* Group-by with an aggregate over a derived key, on the GPU: the rows of the
+ * device-resident result are binned by a u64 key derived from each row, and
+ * per bin come back the key, the rows (bin_words), the wrapping u64 sum of
+ * their counts (bin_tokens) and the lowest table index of a row with that key
+ * (first_row).  ("Group" means an engine group in this interface, so the call
+ * is a histogram with bins.)  The keys:
+ *   MOX_HIST_COUNT  the row's count: the frequency spectrum (count of counts),
+ *                   the input of Good-Turing smoothing and Zipf plots,
+ *   MOX_HIST_BYTES  the word's length in bytes,
+ *   MOX_HIST_CHARS  the word's character starts: bytes b with
+ *                   (b & 0xC0) != 0x80, mox_rekey_result's rule; for valid
+ *                   UTF-8 the word's characters,
+ *   MOX_HIST_FIRST  the word's first character.  The window is the word's
+ *                   first byte plus the continuation bytes ((b & 0xC0) == 0x80)
+ *                   that follow it, at most 4 bytes in all; a word that opens
+ *                   with continuation bytes keeps them, as the re-keying does.
+ *                   key = the window's bytes packed big-endian into bits 39..8
+ *                   (byte 0 in bits 39..32) and the window's length in bits
+ *                   7..0, so ascending keys are the windows in bytewise order,
+ *                   a proper prefix first.  For valid UTF-8 the window is the
+ *                   first character's encoding.  An empty word's key is 0 (a
+ *                   table holds no empty word today).
+ * keys come out ascending and all distinct.  With MOX_HIST_RANGE only rows
+ * [first, min(first + rows, N)) are binned, as mox_top_rows takes them (a
+ * range from mox_find_ranges(MOX_FIND_PREFIX): the histogram of the words
+ * under a prefix); first_row stays absolute, an index into the whole table.
+ * The call only reads.  The result, its buffers, every state flag (pass,
+ * exchanged, sorted, ranked, folded) and the accumulator are exactly what they
+ * were.  It never sorts the table, MOX_F_SORT_BYTES or not: bins do not depend
+ * on row order except first_row, which is an index into the table as it lies
+ * in device memory at the call -- the row mox_fetch_rows(first_row, 1) returns.
+ * Works on every form of result: a run's, mox_reduce_pairs, exchanged,
+ * gathered, mox_run_shards, sorted, ranked, filtered, re-keyed, joined, the
+ * accumulator's total.  Completes pending asynchronous passes first.  An engine
+ * group: member 0's gathered result.
+ * Only 4 x bins u64 values and a few totals come back: nothing sized by the
+ * table crosses PCIe and no host pass runs over rows.
+ * Small cases: an empty result or an empty range gives n == 0 with valid
+ * pointers, and nothing runs on the device; one row gives one bin; when every
+ * key is 0 there is one bin and no radix pass (digit_passes == 0).
+ * Sums: bin_tokens and tokens wrap as u64, like every other sum here.  For
+ * MOX_HIST_COUNT bin_tokens[i] == keys[i] * bin_words[i] mod 2^64.  The sum of
+ * bin_words is words; the sum of bin_tokens is tokens, which equals the
+ * result's tokens when no range is given.  These identities are checked on the
+ * host before anything is handed out: a mismatch is MOX_EHIP ("inconsistent
+ * totals"), as in mox_rank_result.  The sums are deterministic: no atomic adds
+ * a count.
+ * Ranked tables: on a result ranked by mox_rank_result the MOX_HIST_COUNT bins
+ * are contiguous row ranges [first_row, first_row + bin_words), so
+ * mox_fetch_rows(first_row[i], bin_words[i]) is "all words that occur keys[i]
+ * times".
+ * Distributed use: after mox_exchange the ranks own disjoint words, so the
+ * ranks' bins merge by key and words and tokens add up without a gather;
+ * first_row is per rank.
+ * Cost: COUNT and BYTES never read a word byte, FIRST reads at most 4 bytes per
+ * word, CHARS makes one pass over the word bytes.  Then come
+ * ceil(bitlen(max key) / 8) radix passes over the rows (mox_rank_result's sort,
+ * sharing its scratch) and one pass for the bins.  There is no cap on bins:
+ * all-distinct counts give bins == rows.  Device scratch: 8 bytes per row for a
+ * derived key, 24 bytes per row for the sort, 48 bytes per bin; it lives in the
+ * engine and is freed by mox_engine_destroy.
+ * The table is library-owned until mox_hist_free (NULL is fine).
+ * MOX_ESTATE: no result yet.  MOX_EINVAL: a NULL engine, spec or out, an
+ * unknown key or flag, a reserved word that is not 0, first or rows not 0
+ * without MOX_HIST_RANGE, more than MOX_HIST_MAX_WORDS rows in the range.
+ * MOX_ENOMEM: scratch or host memory cannot be allocated.  After any error
+ * *out and *info are untouched and the engine is usable.
+ * MOX_HIST_GRID=<workgroups> (tests; read at each call) caps every grid of the
+ * call, the shared sort's grids included.  MOX_TEST_FAIL_HIST=1 (tests; read at
+ * each call) returns MOX_ENOMEM after the bins are counted and before anything
+ * is copied out. */
+#define MOX_HIST_COUNT 0u  /* key = the row's count: the frequency spectrum */
+#define MOX_HIST_BYTES 1u  /* key = the word's length in bytes */
+#define MOX_HIST_CHARS 2u  /* key = the word's character starts: bytes b with (b & 0xC0) != 0x80
+                              (mox_rekey_result's rule; for valid UTF-8: its characters) */
+#define MOX_HIST_FIRST 3u  /* key = the word's first character (above) */
+#define MOX_HIST_RANGE 0x1u /* flags: only rows [first, min(first + rows, N)), as mox_top_rows takes them */
+#define MOX_HIST_MAX_WORDS 0xFFFFFFFFull   /* rows histogrammed per call: row indices travel as u32 */
+typedef struct mox_hist {
+  uint32_t key, flags;
+  uint64_t first, rows;     /* both must be 0 without MOX_HIST_RANGE; with it rows == 0 is the empty range */
+  uint64_t reserved[4];     /* must be 0 */
+} mox_hist;                 /* 56 bytes */
+typedef struct mox_hist_table {   /* library-owned until mox_hist_free */
+  uint64_t n;                     /* bins: distinct keys among the rows */
+  uint64_t words, tokens;         /* rows histogrammed, and the wrapping u64 sum of their counts */
+  const uint64_t* keys;           /* [n] ascending, all distinct */
+  const uint64_t* bin_words;      /* [n] rows with this key (>= 1) */
+  const uint64_t* bin_tokens;     /* [n] wrapping u64 sum of their counts */
+  const uint64_t* first_row;      /* [n] lowest table index (absolute, not range-relative) of a row with this key */
+} mox_hist_table;
+typedef struct mox_hist_info {
+  uint64_t words, tokens, bins, max_key, digit_passes, device_bytes;
+  double ms;
+  uint64_t reserved[4];
+} mox_hist_info;
+int mox_hist_result(mox_engine* e, const mox_hist* h, mox_hist_table** out, mox_hist_info* info /* may be NULL */);
+void mox_hist_free(mox_hist_table* t);
+
 int mox_get_stats(const mox_engine* e, mox_stats* out);
 
 /* device memory helpers so callers need no HIP headers */

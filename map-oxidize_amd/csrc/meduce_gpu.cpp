@@ -52,6 +52,15 @@
 // --chunk, together with either option is a usage error, and so are both
 // options together: exit status 2.  Without the options every output is what
 // it always was.
+// --histogram KEY (repeatable; KEY is count, bytes, chars or first; anything
+// else is a usage error: exit status 2) prints, after everything else,
+// "Histogram {KEY}: {bins} bins, {words} words, {tokens} tokens" and one
+// "{key}\t{words}\t{tokens}" line per bin, keys ascending: the words and tokens
+// per count (the frequency spectrum), per word length in bytes or characters,
+// or per first character, binned on the device (mox_hist_result).  The key is
+// in decimal; for first it is the character's bytes.  The histogram is read
+// from the result as it stands at that point, after any filter, re-key or
+// ranking.  Without the option every output is what it always was.
 // Exit status 1 with a message on stderr on any error, like `main` returning Err.
 #include <cstdio>
 #include <cstdlib>
@@ -68,7 +77,7 @@ int main(int argc, char** argv) {
   std::string out = "final_result.txt";
   int device = -1;
   unsigned long long chunk = 0;
-  std::vector<std::string> words, prefixes;
+  std::vector<std::string> words, prefixes, hists;
   unsigned long long min_count = 0;
   std::string stop_path, base_path;
   int n_not_in = 0, n_also_in = 0;
@@ -79,6 +88,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) chunk = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--word") && i + 1 < argc) words.push_back(argv[++i]);
     else if (!strcmp(argv[i], "--prefix") && i + 1 < argc) prefixes.push_back(argv[++i]);
+    else if (!strcmp(argv[i], "--histogram") && i + 1 < argc) hists.push_back(argv[++i]);
     else if (!strcmp(argv[i], "--min-count") && i + 1 < argc) min_count = strtoull(argv[++i], nullptr, 10);
     else if (!strcmp(argv[i], "--stop") && i + 1 < argc) { stop_path = argv[++i]; have_stop = true; }
     else if (!strcmp(argv[i], "--not-in") && i + 1 < argc) { base_path = argv[++i]; n_not_in++; }
@@ -88,6 +98,14 @@ int main(int argc, char** argv) {
     else paths.push_back(argv[i]);
   }
   if (paths.empty()) paths.push_back("shakes.txt");
+  const char* const hist_names[4] = {"count", "bytes", "chars", "first"};  // MOX_HIST_COUNT .. MOX_HIST_FIRST
+  std::vector<uint32_t> hist_keys;
+  for (const std::string& k : hists) {
+    uint32_t key = 0;
+    while (key < 4 && k != hist_names[key]) key++;
+    if (key == 4) { fprintf(stderr, "Usage: --histogram count|bytes|chars|first\n"); return 2; }
+    hist_keys.push_back(key);
+  }
   const bool join = n_not_in || n_also_in;
   if (n_not_in && n_also_in) { fprintf(stderr, "Usage: --not-in and --also-in exclude each other\n"); return 2; }
   if (n_not_in + n_also_in > 1) { fprintf(stderr, "Usage: one --not-in or --also-in\n"); return 2; }
@@ -191,6 +209,25 @@ int main(int argc, char** argv) {
       fwrite(pt->bytes + pt->offs[j], 1, pt->offs[j + 1] - pt->offs[j], stdout);
       printf(": %llu\n", (unsigned long long)pt->counts[j]);
     }
+  }
+  for (size_t i = 0; i < hist_keys.size() && rc == MOX_OK; i++) {
+    mox_hist h;
+    memset(&h, 0, sizeof h);
+    h.key = hist_keys[i];
+    mox_hist_table* ht = nullptr;
+    rc = mox_hist_result(e, &h, &ht, nullptr);
+    if (rc != MOX_OK) break;
+    printf("Histogram %s: %llu bins, %llu words, %llu tokens\n", hists[i].c_str(), (unsigned long long)ht->n, (unsigned long long)ht->words,
+           (unsigned long long)ht->tokens);
+    for (uint64_t b = 0; b < ht->n; b++) {
+      if (h.key == MOX_HIST_FIRST) {
+        for (uint64_t x = 0; x < (ht->keys[b] & 0xFF); x++) putchar((int)((ht->keys[b] >> (32 - 8 * x)) & 0xFF));
+      } else {
+        printf("%llu", (unsigned long long)ht->keys[b]);
+      }
+      printf("\t%llu\t%llu\n", (unsigned long long)ht->bin_words[b], (unsigned long long)ht->bin_tokens[b]);
+    }
+    mox_hist_free(ht);
   }
   if (rc != MOX_OK) fprintf(stderr, "Error: %s\n", mox_last_error());
   for (mox_table* pt : p_top) mox_table_free(pt);

@@ -1,7 +1,7 @@
 // Device-side helpers shared by the kernels over the device-resident result
 // table (counts, offs, bytes): mox_bsort.hip, mox_topk.hip, mox_text.hip,
 // mox_accum.hip, mox_lookup.hip, mox_filter.hip, mox_rank.hip, mox_rekey.hip,
-// mox_find.hip, mox_join.hip; mox_pack.h builds the pieces of the two receive-layout
+// mox_find.hip, mox_join.hip, mox_hist.hip; mox_pack.h builds the pieces of the two receive-layout
 // packers on them, mox_wordhash.h the word hash and compare of the lookup and the join.
 // Everything is forced inline: a kernel that uses a helper compiles to what it compiled to
 // with the helper's body written out.
@@ -19,7 +19,9 @@
 // pk_long_lane / pk_long_wave and the lookup's long words: up to 15 bytes past
 // the word's end), the 16 bytes from o on in one load (the lookup's
 // short path, the filter's prefix: up to 15 bytes past a 1-byte word) and the
-// sort's window (two aligned loads).  Whatever is read past a word is masked by
+// sort's window (two aligned loads), and the histogram's keys (8-byte loads from
+// o on, 8 bytes apart: up to 7 bytes past the word's end; the 4 bytes from o on: up
+// to 3 bytes past a 1-byte word).  Whatever is read past a word is masked by
 // the word's length (mask_low) before it is used, and nothing is ever written
 // past a word: copy_lane and copy_wave touch [0, len) on both sides only.
 #pragma once

@@ -1069,6 +1069,7 @@ void mox_engine_destroy(mox_engine* e) {
   rekey_free(e);
   find_free(e);
   join_free(e);
+  hist_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

@@ -5,8 +5,8 @@
 // the device-resident accumulator (mox_accum.hip), the device lookup
 // (mox_lookup.hip), the device filter (mox_filter.hip), the device ranking
 // (mox_rank.hip), the device re-keying (mox_rekey.hip), the device search
-// of the sorted result (mox_find.hip) and the device join against the total
-// (mox_join.hip).  The device-side
+// of the sorted result (mox_find.hip), the device join against the total
+// (mox_join.hip) and the device histograms of the result (mox_hist.hip).  The device-side
 // helpers those kernels share are in mox_dev.h and mox_pack.h (the two
 // packers); the host-side ones (result_begin, table_reserve and the
 // declarations around it, Received: the hand-off to the reduce-only pass) are below.
@@ -219,6 +219,9 @@ struct mox_engine {
   // result's rows, matched and substituted counts); the match bitmap, the tile
   // arrays and the output are the filter's (f_tmp, f_tab)
   DevBuf j_tmp;
+  // device histograms (mox_hist.hip): scratch (the derived keys, the tile heads
+  // and tile sums), the bins on the device, the pinned block of the totals
+  DevBuf hg_tmp, hg_out, hg_pin;
   Corpus last_corpus{};
   mox_stats stats{};
   hipEvent_t ev[12]{};
@@ -348,6 +351,20 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
 void filter_free(mox_engine* e);
 // ---- mox_rank.hip
 void rank_free(mox_engine* e);
+// The stable order of n u64 keys on the device (the ranking's radix sort of (key ^ flip,
+// row) pairs over r_tmp).  Valid until the next call that uses r_tmp.
+struct RankOrder {
+  const uint64_t* keys = nullptr;       // [n] key ^ flip in ascending order; NULL: no pass ran (every key is 0), the order is the source's
+  const uint32_t* rows = nullptr;       // [n] the source row of each; NULL with keys
+  uint64_t flip = 0, max_key = 0;       // max_key: the largest key as given (not flipped)
+  uint32_t passes = 0;                  // ceil(bitlen(max_key) / 8)
+  const uint32_t* d_counted = nullptr;  // device: the rows the last pass counted (the caller checks it against n); NULL with keys
+  void* extra = nullptr;                // device: the caller's extra bytes behind the sort's scratch
+};
+// cap: the grid cap of every launch; extra: bytes of the caller's own scratch in r_tmp.  n >= 1.
+int rank_order(mox_engine* e, const uint64_t* d_keys, uint64_t n, uint64_t flip, uint64_t cap, size_t extra, RankOrder* out);
+// ---- mox_hist.hip
+void hist_free(mox_engine* e);
 // ---- mox_rekey.hip
 void rekey_free(mox_engine* e);
 // ---- mox_find.hip

@@ -33,6 +33,8 @@
 //       of its step (ballot rank).  Pass 0 reads the counts themselves and
 //       takes the row number as the index; every pass writes (u64 key, u32
 //       index) to the other of two scratch arrays.
+//     Steps 1 and 2 are the host function rank_order (mox_host.h), which takes
+//     any u64 key array: the histograms (mox_hist.hip) sort their keys with it.
 //  3. k_rk_len: per tile the bytes of its words in the new order; k_rk_offs (one
 //     workgroup): their exclusive scan, the total behind them (= the table's
 //     bytes, checked by the host).
@@ -381,6 +383,66 @@ void rank_free(mox_engine* e) {
   e->h_rmax = nullptr;
 }
 
+// The stable order of n u64 keys on the device by key ^ flip (steps 1 and 2 of
+// the file's header): the ranking's, and the histogram's over its own keys.
+// extra: bytes of the caller's own scratch, carved behind the sort's in r_tmp.
+int rank_order(mox_engine* e, const uint64_t* d_keys, uint64_t n, uint64_t flip, uint64_t cap, size_t extra, RankOrder* out) {
+  hipStream_t st = e->stream;
+  const Seq q = seq_of(e);
+  int rc;
+  const uint64_t nt = (n + RK_TILE - 1) / RK_TILE;
+  const uint32_t grid = (uint32_t)std::min(nt, cap);
+  // scratch: [block maxima] [keys A] [keys B] [rows A] [rows B] [digit counts 256 nt] [chunk sums nc + 1] [the caller's extra bytes]
+  // (every array a multiple of 256 bytes)
+  const uint64_t m = (uint64_t)RK_DIGITS * nt, nc = (m + RK_CHUNK - 1) / RK_CHUNK;
+  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
+  const size_t bm_b = up(8 * cap), key_b = up(8 * n), idx_b = up(4 * n), th_b = up(4 * m), cs_b = up(4 * (nc + 1)), tb_b = up(extra);
+  if ((rc = grow_dev(e->r_tmp, bm_b + 2 * key_b + 2 * idx_b + th_b + cs_b + tb_b))) return rc;
+  if (!e->h_rmax) HIPCHK(hipHostMalloc((void**)&e->h_rmax, 8 * (8 * (size_t)e->n_cu + 8), hipHostMallocDefault));
+  uint8_t* p = (uint8_t*)e->r_tmp.p;
+  uint64_t* bm = (uint64_t*)p;
+  uint64_t* keys[2] = {(uint64_t*)(p + bm_b), (uint64_t*)(p + bm_b + key_b)};
+  uint32_t* rows[2] = {(uint32_t*)(p + bm_b + 2 * key_b), (uint32_t*)(p + bm_b + 2 * key_b + idx_b)};
+  uint32_t* th = (uint32_t*)(p + bm_b + 2 * key_b + 2 * idx_b);
+  uint32_t* cs = (uint32_t*)((uint8_t*)th + th_b);
+
+  // 1. the largest key and the digits it has
+  hipLaunchKernelGGL(k_rk_max, dim3(grid), dim3(RK_T), 0, st, d_keys, n, bm);
+  q.step("k_rk_max");
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(e->h_rmax, bm, 8 * (size_t)grid, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  uint64_t max_key = 0;
+  for (uint32_t g = 0; g < grid; g++) max_key = std::max<uint64_t>(max_key, e->h_rmax[g]);
+  uint32_t passes = 0;
+  while (passes < 8 && (max_key >> (8 * passes))) passes++;
+
+  // 2. the radix passes, low digit first
+  const uint32_t sgrid = (uint32_t)std::min(nc, cap);
+  for (uint32_t k = 0; k < passes; k++) {
+    const RkPass P{k ? keys[(k - 1) & 1] : d_keys, k ? rows[(k - 1) & 1] : nullptr, keys[k & 1], rows[k & 1], k ? 0ull : flip, n, nt, 8 * k};
+    hipLaunchKernelGGL(k_rk_hist, dim3(grid), dim3(RK_T), 0, st, P, th);
+    q.step("k_rk_hist");
+    hipLaunchKernelGGL(k_rk_scan_part, dim3(sgrid), dim3(RK_T), 0, st, (const uint32_t*)th, m, cs);
+    q.step("k_rk_scan_part");
+    hipLaunchKernelGGL(k_rk_scan_top, dim3(1), dim3(RK_TOP_T), 0, st, cs, nc);
+    q.step("k_rk_scan_top");
+    hipLaunchKernelGGL(k_rk_scan_apply, dim3(sgrid), dim3(RK_T), 0, st, th, m, (const uint32_t*)cs);
+    q.step("k_rk_scan_apply");
+    hipLaunchKernelGGL(k_rk_scatter, dim3(grid), dim3(RK_T), 0, st, P, (const uint32_t*)th);
+    q.step("k_rk_scatter");
+    HIPCHK(hipGetLastError());
+  }
+  out->keys = passes ? keys[(passes - 1) & 1] : nullptr;
+  out->rows = passes ? rows[(passes - 1) & 1] : nullptr;
+  out->flip = passes ? flip : 0ull;
+  out->max_key = max_key;
+  out->passes = passes;
+  out->d_counted = passes ? cs + nc : nullptr;
+  out->extra = (uint8_t*)cs + cs_b;
+  return MOX_OK;
+}
+
 }  // namespace mox_host
 
 extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* info) {
@@ -419,50 +481,15 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
   const RkTab T{r.counts, r.offs, r.bytes, r.n, r.nb, (r.n + RK_TILE - 1) / RK_TILE};
   const uint64_t cap = grid_cap(e, "MOX_RANK_GRID");
   const uint32_t grid = (uint32_t)std::min(T.nt, cap);
-  // scratch: [block maxima] [keys A] [keys B] [rows A] [rows B] [digit counts 256 nt] [chunk sums nc + 1] [tile bytes nt + 1]
-  // (every array a multiple of 256 bytes)
-  const uint64_t m = (uint64_t)RK_DIGITS * T.nt, nc = (m + RK_CHUNK - 1) / RK_CHUNK;
-  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
-  const size_t bm_b = up(8 * cap), key_b = up(8 * T.n), idx_b = up(4 * T.n), th_b = up(4 * m), cs_b = up(4 * (nc + 1)), tb_b = up(8 * (T.nt + 1));
-  if ((rc = grow_dev(e->r_tmp, bm_b + 2 * key_b + 2 * idx_b + th_b + cs_b + tb_b))) return rc;
-  if (!e->h_rmax) HIPCHK(hipHostMalloc((void**)&e->h_rmax, 8 * (8 * (size_t)e->n_cu + 8), hipHostMallocDefault));
-  uint8_t* p = (uint8_t*)e->r_tmp.p;
-  uint64_t* bm = (uint64_t*)p;
-  uint64_t* keys[2] = {(uint64_t*)(p + bm_b), (uint64_t*)(p + bm_b + key_b)};
-  uint32_t* rows[2] = {(uint32_t*)(p + bm_b + 2 * key_b), (uint32_t*)(p + bm_b + 2 * key_b + idx_b)};
-  uint32_t* th = (uint32_t*)(p + bm_b + 2 * key_b + 2 * idx_b);
-  uint32_t* cs = (uint32_t*)((uint8_t*)th + th_b);
-  uint64_t* tb = (uint64_t*)((uint8_t*)cs + cs_b);
-
-  // 1. the largest count and the digits it has
-  hipLaunchKernelGGL(k_rk_max, dim3(grid), dim3(RK_T), 0, st, T.counts, T.n, bm);
-  q.step("k_rk_max");
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_rmax, bm, 8 * (size_t)grid, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (uint32_t g = 0; g < grid; g++) ri.max_count = std::max<uint64_t>(ri.max_count, e->h_rmax[g]);
-  uint32_t passes = 0;
-  while (passes < 8 && (ri.max_count >> (8 * passes))) passes++;
-  ri.digit_passes = passes;
-
-  // 2. the radix passes, low digit first
+  // 1. and 2. the order (rank_order), with the tile bytes [nt + 1] behind its scratch
   const uint64_t flip = (flags & MOX_RANK_ASCENDING) ? 0ull : ~0ull;
-  const uint32_t sgrid = (uint32_t)std::min(nc, cap);
-  for (uint32_t k = 0; k < passes; k++) {
-    const RkPass P{k ? keys[(k - 1) & 1] : T.counts, k ? rows[(k - 1) & 1] : nullptr, keys[k & 1], rows[k & 1], k ? 0ull : flip, T.n, T.nt, 8 * k};
-    hipLaunchKernelGGL(k_rk_hist, dim3(grid), dim3(RK_T), 0, st, P, th);
-    q.step("k_rk_hist");
-    hipLaunchKernelGGL(k_rk_scan_part, dim3(sgrid), dim3(RK_T), 0, st, (const uint32_t*)th, m, cs);
-    q.step("k_rk_scan_part");
-    hipLaunchKernelGGL(k_rk_scan_top, dim3(1), dim3(RK_TOP_T), 0, st, cs, nc);
-    q.step("k_rk_scan_top");
-    hipLaunchKernelGGL(k_rk_scan_apply, dim3(sgrid), dim3(RK_T), 0, st, th, m, (const uint32_t*)cs);
-    q.step("k_rk_scan_apply");
-    hipLaunchKernelGGL(k_rk_scatter, dim3(grid), dim3(RK_T), 0, st, P, (const uint32_t*)th);
-    q.step("k_rk_scatter");
-    HIPCHK(hipGetLastError());
-  }
-  const RkOrder O{passes ? keys[(passes - 1) & 1] : nullptr, passes ? rows[(passes - 1) & 1] : nullptr, passes ? flip : 0ull};
+  RankOrder ro;
+  if ((rc = rank_order(e, T.counts, T.n, flip, cap, 8 * (T.nt + 1), &ro))) return rc;
+  ri.max_count = ro.max_key;
+  ri.digit_passes = ro.passes;
+  const uint32_t passes = ro.passes;
+  uint64_t* tb = (uint64_t*)ro.extra;
+  const RkOrder O{ro.keys, ro.rows, ro.flip};
 
   // 3. the new offsets
   hipLaunchKernelGGL(k_rk_len, dim3(grid), dim3(RK_T), 0, st, T, O, tb);
@@ -472,7 +499,7 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
   HIPCHK(hipGetLastError());
   uint64_t* h_tot = e->h_rmax;  // the rows the last pass counted (a u32: the low half of a zeroed word), the bytes of the new order
   h_tot[0] = h_tot[1] = 0;
-  if (passes) HIPCHK(hipMemcpyAsync(h_tot, cs + nc, 4, hipMemcpyDeviceToHost, st));
+  if (passes) HIPCHK(hipMemcpyAsync(h_tot, ro.d_counted, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(h_tot + 1, tb + T.nt, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if ((passes && h_tot[0] != T.n) || h_tot[1] != T.nb)

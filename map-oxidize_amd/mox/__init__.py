@@ -60,6 +60,21 @@ FIND_PREFIX = 1  # MOX_FIND_PREFIX: the rows whose word starts with the key
 FIND_LOWER = 2   # MOX_FIND_LOWER: first = last = the number of rows bytewise below the key
 FIND_MAX = 1 << 20  # MOX_FIND_MAX: the most keys one Engine.find call takes
 _FIND_MODES = {"exact": FIND_EXACT, "prefix": FIND_PREFIX, "lower": FIND_LOWER}
+HIST_COUNT = 0  # MOX_HIST_COUNT: Engine.histogram bins by the row's count (the frequency spectrum)
+HIST_BYTES = 1  # MOX_HIST_BYTES: ... by the word's length in bytes
+HIST_CHARS = 2  # MOX_HIST_CHARS: ... by the word's character starts (bytes b with (b & 0xC0) != 0x80)
+HIST_FIRST = 3  # MOX_HIST_FIRST: ... by the word's first character (hist_first_bytes decodes the key)
+HIST_RANGE = 0x1  # MOX_HIST_RANGE: only rows [first, first + rows)
+HIST_MAX_WORDS = (1 << 32) - 1  # MOX_HIST_MAX_WORDS: the most rows one Engine.histogram call takes
+_HIST_KEYS = {"count": HIST_COUNT, "bytes": HIST_BYTES, "chars": HIST_CHARS, "first": HIST_FIRST}
+
+
+def hist_first_bytes(key):
+    """The bytes of a HIST_FIRST key: the word's first byte and the continuation
+    bytes behind it, at most 4 (for valid UTF-8: the first character's encoding);
+    b"" for key 0."""
+    key = int(key)
+    return (key >> 8).to_bytes(4, "big")[:key & 0xFF]
 
 
 class MoxError(RuntimeError):
@@ -246,6 +261,44 @@ class FindInfo(ctypes.Structure):
     ]
 
 
+class Hist(ctypes.Structure):
+    """mox_hist: the key (HIST_*), the flags (HIST_RANGE) and the row range."""
+    _fields_ = [
+        ("key", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("first", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class HistInfo(ctypes.Structure):
+    """mox_hist_info: rows and tokens histogrammed, bins, the largest key, radix passes, device bytes, ms."""
+    _fields_ = [
+        ("words", ctypes.c_uint64),
+        ("tokens", ctypes.c_uint64),
+        ("bins", ctypes.c_uint64),
+        ("max_key", ctypes.c_uint64),
+        ("digit_passes", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms", ctypes.c_double),
+        ("reserved", ctypes.c_uint64 * 4),
+    ]
+
+
+class _HistTable(ctypes.Structure):
+    """mox_hist_table: library-owned until mox_hist_free."""
+    _fields_ = [
+        ("n", ctypes.c_uint64),
+        ("words", ctypes.c_uint64),
+        ("tokens", ctypes.c_uint64),
+        ("keys", ctypes.POINTER(ctypes.c_uint64)),
+        ("bin_words", ctypes.POINTER(ctypes.c_uint64)),
+        ("bin_tokens", ctypes.POINTER(ctypes.c_uint64)),
+        ("first_row", ctypes.POINTER(ctypes.c_uint64)),
+    ]
+
+
 class _Table(ctypes.Structure):
     _fields_ = [
         ("n", ctypes.c_uint64),
@@ -357,6 +410,8 @@ def lib(path=None):
             "mox_rekey_result": ([VP, P(Rekey), P(RekeyInfo)], I),
             "mox_find_ranges": ([VP, VP, P(U64), U64, ctypes.c_uint32, P(U64), P(U64), P(U64), P(FindInfo)], I),
             "mox_top_rows": ([VP, U64, U64, sz, P(P(_Table))], I),
+            "mox_hist_result": ([VP, P(Hist), P(P(_HistTable)), P(HistInfo)], I),
+            "mox_hist_free": ([P(_HistTable)], None),
             "mox_get_stats": ([VP, P(Stats)], I),
             "mox_device_alloc": ([VP, sz, P(VP)], I),
             "mox_device_free": ([VP, VP], I),
@@ -819,6 +874,39 @@ class Engine:
         does not sort behind the caller's back."""
         first, last = self.find([prefix], "prefix", with_sums=False)
         return self.top_rows(int(first[0]), int(last[0] - first[0]), k)
+
+    # -- histograms of the result on the device (mox_hist_result)
+    def histogram(self, key="count", first=None, n=None, with_info=False):
+        """Bin the rows of the device-resident result by a derived key on the GPU
+        (mox_hist_result; the call only reads the result).  ``key``: "count" (the
+        frequency spectrum), "bytes", "chars", "first" (the first character:
+        hist_first_bytes decodes a key), or a HIST_* constant.  ``first`` / ``n``
+        given: only rows [first, first + n), as top_rows takes them.  Returns
+        (keys, bin_words, bin_tokens, first_row, words, tokens[, info]): four
+        uint64 arrays of one entry per bin, keys ascending, first_row the lowest
+        table index of a row with that key; words and tokens the rows binned and
+        the wrapping u64 sum of their counts."""
+        import numpy as np
+
+        h = Hist()
+        h.key = _HIST_KEYS.get(key, key)
+        if first is not None or n is not None:
+            h.flags = HIST_RANGE
+            h.first = 0 if first is None else first
+            h.rows = (1 << 64) - 1 if n is None else n
+        info = HistInfo()
+        t = ctypes.POINTER(_HistTable)()
+        self._c(self._L.mox_hist_result(self._h, ctypes.byref(h), ctypes.byref(t), ctypes.byref(info)))
+        try:
+            c = t.contents
+            g = int(c.n)
+            out = tuple(np.ctypeslib.as_array(getattr(c, f), shape=(g,)).copy() if g else np.zeros(0, dtype=np.uint64)
+                        for f in ("keys", "bin_words", "bin_tokens", "first_row")) + (int(c.words), int(c.tokens))
+        finally:
+            self._L.mox_hist_free(t)
+        if with_info:
+            out += ({k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"},)
+        return out
 
     def stats(self):
         s = Stats()

@@ -136,6 +136,30 @@ def sum_finds(per_rank):
     return rows, sums
 
 
+def sum_histograms(parts):
+    """Global bins from per-rank histograms: ``parts[r]`` is rank r's
+    ``Engine.histogram(key)`` -- (keys, bin_words, bin_tokens, ...) -- of the same
+    key after an exchange.  The ranks then own disjoint words, so bins merge by
+    key and their words and tokens add up (wrapping as u64, as on the device) to
+    what a gather followed by one histogram gives, without gathering.  Returns
+    (keys, bin_words, bin_tokens, words, tokens): keys ascending; first_row is per
+    rank and is dropped.  ValueError when a part's arrays differ in length."""
+    import numpy as np
+
+    arrs = [tuple(np.asarray(a, dtype=np.uint64).reshape(-1) for a in p[:3]) for p in parts]
+    if any(len(p) < 3 or p[0].size != p[1].size or p[0].size != p[2].size for p in arrs):
+        raise ValueError("a histogram needs keys, bin_words and bin_tokens of one length")
+    if not arrs:
+        z = np.zeros(0, dtype=np.uint64)
+        return z, z.copy(), z.copy(), 0, 0
+    keys, inv = np.unique(np.concatenate([p[0] for p in arrs]), return_inverse=True)
+    words = np.zeros(keys.size, dtype=np.uint64)
+    tokens = np.zeros(keys.size, dtype=np.uint64)
+    np.add.at(words, inv, np.concatenate([p[1] for p in arrs]))  # (unsigned adds wrap)
+    np.add.at(tokens, inv, np.concatenate([p[2] for p in arrs]))
+    return keys, words, tokens, int(words.sum(dtype=np.uint64)), int(tokens.sum(dtype=np.uint64))
+
+
 def sum_joins(infos):
     """The global join info from per-rank joins: ``infos[r]`` is rank r's
     ``Engine.join_total(...)`` after a hash-owner exchange (no MOX_F_SORT_BYTES),
