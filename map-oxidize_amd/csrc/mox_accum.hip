@@ -203,15 +203,6 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
   }
 }
 
-namespace mox_host {
-
-void accum_free(mox_engine* e) {
-  free_bufs({&e->a_tab[0], &e->a_tab[1], &e->a_tab[2], &e->a_tc});
-  e->acc = mox_engine::Acc{};
-}
-
-}  // namespace mox_host
-
 namespace {
 
 AcTab ac_tab(const uint64_t* counts, const uint64_t* offs, const uint8_t* bytes, uint64_t n) {
@@ -223,8 +214,6 @@ AcTab ac_tab(const uint64_t* counts, const uint64_t* offs, const uint8_t* bytes,
 void acc_as_result(mox_engine* e) {
   mox_engine::Res& r = e->res;
   res_point_at(r, e->a_tab, e->acc.n, e->acc.nb, e->acc.tokens);
-  r.pass = false;
-  r.exchanged = false;
   r.sorted = e->acc.sorted;
   r.ranked = e->acc.ranked;
   r.folded = true;
@@ -374,7 +363,8 @@ extern "C" int mox_accumulate_reset(mox_engine* e) {
   HIPCHK(hipStreamSynchronize(e->stream));
   // a result that lives in the total's buffers (after a failed fold) goes with them
   if (e->have_result && e->res.counts == (const uint64_t*)e->a_tab[0].p && e->a_tab[0].p) e->have_result = false;
-  accum_free(e);
+  free_bufs({&e->a_tab[0], &e->a_tab[1], &e->a_tab[2], &e->a_tc});
+  e->acc = mox_engine::Acc{};
   // the last run's result, if any, may be folded into the fresh total
   e->res.folded = false;
   return MOX_OK;

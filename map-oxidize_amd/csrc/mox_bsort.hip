@@ -702,12 +702,6 @@ int radix_sort(mox_engine* e, BSort& s, uint64_t n, int nd, bool zeroed) {
 
 }  // namespace
 
-void bsort_free(mox_engine* e) {
-  free_bufs({&e->s_counts, &e->s_offs, &e->s_bytes, &e->s_tmp});
-  if (e->h_bsort) (void)hipHostFree(e->h_bsort);
-  e->h_bsort = nullptr;
-}
-
 // The engine's result table (e->res) in bytewise order, on its GPU: the
 // sorted copy lives in s_counts / s_offs / s_bytes and becomes the result.
 // Scratch (s_tmp) is engine-owned and reused across calls: about 60 bytes per
@@ -745,64 +739,81 @@ int bsort_once(mox_engine* e, bool checked) {
   // as failed, so the record arrays borrow the pass buffers as on a full GPU
   uint64_t tmp_max = ~0ull;
   if (const char* v = getenv("MOX_BSORT_TMP_MAX")) tmp_max = strtoull(v, nullptr, 10);
-  // (every array a multiple of 256 bytes: what follows stays aligned for its 8-byte atomics)
-  const uint64_t rec = (16 * n + 255) & ~255ull, u64n = (8 * n + 255) & ~255ull, u32n = (4 * n + 255) & ~255ull;
   const uint64_t sums = 8ull * scan_sum_words(n);
   const uint64_t stb = 8ull * (one_region ? 1 : OS_DIGITS) * 256 * ntiles;
   const unsigned int lrun_cap = (unsigned int)std::min<uint64_t>(1u << 20, n / 4 + 16);  // k_bs_longsort's run list
-  const uint64_t small = 8ull * lrun_cap + TICK_BYTES + stb + 2 * OS_DIGITS * 256 * 8 + sums + 256;
   // A, B, S (the tie subset: in the checked mode only; else the radix pass's
   // free ping-pong buffer), pay, fin, pos
-  const uint64_t big[6] = {rec, rec, checked ? rec : 0, rec, u64n, u32n};
-  uint8_t* bp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const uint64_t big[6] = {16 * n, 16 * n, checked ? 16 * n : 0, 16 * n, 8 * n, 4 * n};
+  uint8_t* bor[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // the big arrays that live in borrowed pass buffers
+  uint8_t* bp[6];
+  uint2* lrun;
+  uint64_t *ssum, *total;
+  BSort s;
+  // s_tmp: the big arrays that are not borrowed, then the small ones (every array on a
+  // 256-byte boundary: an odd n leaves the 8-byte atomics behind a 4 n-byte array aligned)
+  auto layout = [&](Carve& c) {
+    for (int k = 0; k < 6; k++) bp[k] = bor[k] ? bor[k] : big[k] ? c.take_bytes(big[k]) : nullptr;
+    lrun = c.take<uint2>(lrun_cap);
+    s.tick = (unsigned int*)c.take_bytes(TICK_BYTES + stb);  // the tickets and the status words are zeroed together
+    s.gh = c.take<unsigned long long>(OS_DIGITS * 256);
+    s.gs = c.take<uint64_t>(OS_DIGITS * 256);
+    ssum = (uint64_t*)c.take_bytes(sums);
+    total = c.take<uint64_t>(8);  // [0] subset size [1] runs
+    s.err = c.take<unsigned int>(48);
+  };
+  auto need_of = [&]() {
+    Carve c;
+    layout(c);
+    return (uint64_t)c.used;
+  };
   int rc;
   if ((rc = table_reserve(e->s_counts, e->s_offs, e->s_bytes, n, nb))) return rc;
-  uint64_t need = small;
-  for (uint64_t b : big) need += b;
+  uint64_t need = need_of();
   rc = need > tmp_max ? (int)MOX_ENOMEM : grow_dev(e->s_tmp, need);
   if (rc == MOX_ENOMEM) {
     (void)hipGetLastError();  // the failed hipMalloc's error is not a later launch's
     const Work& w = e->w;  // (the table is in t_*, or in the gather / sort buffers: never in these)
-    struct Slab { uint8_t* p; uint64_t left; };
-    Slab slab[] = {{(uint8_t*)w.cold, w.cold ? (uint64_t)w.map_grid * NB * w.cold_cap * 16 : 0},
-                   {(uint8_t*)w.uk, w.uk ? w.uniq_cap * 16 : 0},
-                   {(uint8_t*)w.split_k, w.split_k ? w.split_k_cap * 16 : 0},
-                   {(uint8_t*)w.uc, w.uc ? w.uniq_cap * 8 : 0},
-                   {(uint8_t*)w.w, w.w ? w.w_cap * sizeof(WRec) : 0},
-                   {(uint8_t*)w.w_sorted, w.w_sorted ? w.w_cap * sizeof(WRec) : 0},
-                   {(uint8_t*)w.ui, w.ui ? w.uniq_cap * 4 : 0}};
-    need = small;
+    struct Slab { Carve c; uint64_t cap; };
+    Slab slab[] = {{{(uint8_t*)w.cold}, w.cold ? (uint64_t)w.map_grid * NB * w.cold_cap * 16 : 0},
+                   {{(uint8_t*)w.uk}, w.uk ? w.uniq_cap * 16 : 0},
+                   {{(uint8_t*)w.split_k}, w.split_k ? w.split_k_cap * 16 : 0},
+                   {{(uint8_t*)w.uc}, w.uc ? w.uniq_cap * 8 : 0},
+                   {{(uint8_t*)w.w}, w.w ? w.w_cap * sizeof(WRec) : 0},
+                   {{(uint8_t*)w.w_sorted}, w.w_sorted ? w.w_cap * sizeof(WRec) : 0},
+                   {{(uint8_t*)w.ui}, w.ui ? w.uniq_cap * 4 : 0}};
     for (int k = 0; k < 6; k++) {
       if (!big[k]) continue;
       for (auto& sl : slab)
-        if (sl.p && sl.left >= big[k]) {
-          bp[k] = sl.p;
-          const uint64_t used = (big[k] + 255) & ~255ull;
-          sl.p += used;
-          sl.left = sl.left > used ? sl.left - used : 0;
+        if (sl.c.base) {
+          Carve c = sl.c;
+          uint8_t* at = c.take_bytes(big[k]);
+          if (c.used > sl.cap) continue;
+          bor[k] = at;
+          sl.c = c;
           break;
         }
-      if (!bp[k]) need += big[k];
     }
+    need = need_of();
     rc = grow_dev(e->s_tmp, need);
     if (rc) {
       size_t fr = 0, to = 0;
       (void)hipMemGetInfo(&fr, &to);
       (void)hipGetLastError();
       int nbor = 0;
-      for (uint8_t* p : bp) nbor += p != nullptr;
+      for (uint8_t* p : bor) nbor += p != nullptr;
       return fail(MOX_ENOMEM, "bytewise sort: %llu words need %llu scratch bytes besides %d borrowed arrays; %zu of %zu bytes free",
                   (unsigned long long)n, (unsigned long long)need, nbor, fr, to);
     }
   }
   if (rc) return rc;
-  if (!e->h_bsort) HIPCHK(hipHostMalloc((void**)&e->h_bsort, OS_DIGITS * 256 * 8 + 64, hipHostMallocDefault));
-  uint8_t* q = (uint8_t*)e->s_tmp.p;
+  if ((rc = grow_pinned(e->h_bsort, OS_DIGITS * 256 * 8 + 64))) return rc;
+  Carve place{(uint8_t*)e->s_tmp.p};
+  layout(place);
   int n_big = 0, n_borrowed = 0;  // the big arrays in use, and those that live in borrowed pass buffers
   for (int k = 0; k < 6; k++) {
     n_big += big[k] != 0;
-    n_borrowed += bp[k] != nullptr;
-    if (!bp[k] && big[k]) { bp[k] = q; q += big[k]; }
+    n_borrowed += bor[k] != nullptr;
   }
   BRec* A = (BRec*)bp[0];
   BRec* B = (BRec*)bp[1];
@@ -810,17 +821,9 @@ int bsort_once(mox_engine* e, bool checked) {
   BPay* pay = (BPay*)bp[3];
   uint64_t* fin = (uint64_t*)bp[4];
   uint32_t* pos = (uint32_t*)bp[5];
-  uint2* lrun = (uint2*)q; q += 8ull * lrun_cap;
-  BSort s;
-  s.tick = (unsigned int*)q; q += TICK_BYTES;
-  s.status = (uint64_t*)q; q += stb;
+  s.status = (uint64_t*)((uint8_t*)s.tick + TICK_BYTES);
   s.one_region = one_region;
-  s.gh = (unsigned long long*)q; q += OS_DIGITS * 256 * 8;
-  s.gs = (uint64_t*)q; q += OS_DIGITS * 256 * 8;
-  uint64_t* ssum = (uint64_t*)q; q += sums;
-  uint64_t* total = (uint64_t*)q; q += 64;  // [0] subset size [1] runs
-  s.err = (unsigned int*)q;
-  uint64_t* h_tot = (uint64_t*)(e->h_bsort + OS_DIGITS * 256);
+  uint64_t* h_tot = (uint64_t*)e->h_bsort.p + OS_DIGITS * 256;
   // the carve-up keeps every array aligned for its widest access (16-byte
   // record loads, 8-byte atomics and status words), also with borrowed arrays
   {

@@ -9,7 +9,7 @@
 // The slack contract.  Every bytes buffer a result can live in carries
 // TABLE_SLACK (mox_host.h: 64) bytes past the table's nb bytes: t_bytes
 // (realloc_sized), the gather, sort, accumulator, filter and rank outputs
-// (table_reserve).  A word starts at an offset o <= nb, so a kernel may read
+// (table_reserve, mox_result.hip).  A word starts at an offset o <= nb, so a kernel may read
 // past a word without a clamp as long as the read starts no later than the
 // word's first byte and ends less than TABLE_SLACK bytes past o.  The readers
 // that do: the 16 key bytes of a row as three aligned 8-byte loads from o & ~7

@@ -1059,17 +1059,7 @@ void mox_engine_destroy(mox_engine* e) {
   if (!e) return;
   if (e->grp) group_destroy(e);  // the other members and the communicators
   xplan_free(e);
-  bsort_free(e);
-  topk_free(e);
-  text_free(e);
-  accum_free(e);
-  lookup_free(e);
-  filter_free(e);
-  rank_free(e);
-  rekey_free(e);
-  find_free(e);
-  join_free(e);
-  hist_free(e);
+  result_free(e);
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
   for (auto& a : e->aslot) {

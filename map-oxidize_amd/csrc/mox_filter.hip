@@ -307,14 +307,6 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint
   }
 }
 
-namespace mox_host {
-
-void filter_free(mox_engine* e) {
-  free_bufs({&e->f_tab[0][0], &e->f_tab[0][1], &e->f_tab[0][2], &e->f_tab[1][0], &e->f_tab[1][1], &e->f_tab[1][2], &e->f_tmp});
-}
-
-}  // namespace mox_host
-
 namespace {
 
 // A call's scratch in f_tmp: [tile arrays 3 nt | totals 3 | list_found | pad 4] [keep masks 16 nt] [list bitmap]
@@ -326,11 +318,13 @@ struct FlTmp {
 
 // f_tmp grown and laid out for the table T, the totals and (with bitmap) the list bitmap zeroed.
 int fl_scratch(mox_engine* e, const FlTab& T, bool bitmap, FlTmp* s) {
-  const size_t tc_b = (3 * T.nt + 8) * 8, keep_b = T.nt * FL_STEPS * 8, bm_b = bitmap ? ((T.n + 63) / 64) * 8 + 8 : 0;
-  if (int rc = grow_dev(e->f_tmp, tc_b + keep_b + bm_b)) return rc;
-  s->tc = (uint64_t*)e->f_tmp.p;
-  s->keep = (uint64_t*)((uint8_t*)e->f_tmp.p + tc_b);
-  s->listed = (uint32_t*)((uint8_t*)e->f_tmp.p + tc_b + keep_b);
+  const size_t bm_b = bitmap ? ((T.n + 63) / 64) * 8 + 8 : 0;
+  if (int rc = carve_dev(e->f_tmp, [&](Carve& c) {
+        s->tc = c.take<uint64_t>(3 * T.nt + 8);
+        s->keep = c.take<uint64_t>(T.nt * FL_STEPS);
+        s->listed = (uint32_t*)c.take_bytes(bm_b);
+      }))
+    return rc;
   if (T.n) {
     HIPCHK(hipMemsetAsync(s->tc + 3 * T.nt, 0, 64, e->stream));
     if (bitmap) HIPCHK(hipMemsetAsync(s->listed, 0, bm_b, e->stream));
@@ -467,8 +461,6 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   // the kept words are the result: order, sorted and folded as the source had them
   mox_engine::Res& res = e->res;
   res_point_at(res, dst, tot[0], tot[1], tot[2]);
-  res.pass = false;
-  res.exchanged = false;
   return finish();
 }
 
@@ -545,8 +537,6 @@ extern "C" int mox_join_total(mox_engine* e, const mox_join* j, mox_join_info* i
   // the kept rows are the result: order, sorted and folded as R had them; substituted counts are in no count order
   mox_engine::Res& res = e->res;
   res_point_at(res, dst, tot[0], tot[1], tot[2]);
-  res.pass = false;
-  res.exchanged = false;
   if (j->counts != MOX_JOIN_COUNTS_RESULT && tot[0] > 1) res.ranked = false;
   return finish();
 }

@@ -200,16 +200,6 @@ extern "C" __global__ __launch_bounds__(FD_T) void k_fd_sum(FdTab T, FdKeys K, c
   }
 }
 
-namespace mox_host {
-
-void find_free(mox_engine* e) {
-  free_bufs({&e->fd_tmp});
-  if (e->fd_pin.p) (void)hipHostFree(e->fd_pin.p);
-  e->fd_pin = DevBuf{};
-}
-
-}  // namespace mox_host
-
 extern "C" int mox_find_ranges(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint32_t mode, uint64_t* first,
                                uint64_t* last, uint64_t* sums, mox_find_info* info) {
   if (!e) return fail(MOX_EINVAL, "engine is NULL");
@@ -243,19 +233,22 @@ extern "C" int mox_find_ranges(mox_engine* e, const uint8_t* bytes, const uint64
   int rc;
   // device scratch: [first n | last n | control block | sums n] (the part that comes back) | key offsets | tile sums + total | key bytes
   const uint64_t ntiles = (r.n + FD_TILE - 1) / FD_TILE;
-  const size_t head_b = 16 * n + sizeof(FdCtl), out_b = head_b + (sums ? 8 * n : 0), ko_b = 8 * (n + 1), s_b = sums ? 8 * (ntiles + 1) : 0;
-  if ((rc = grow_dev(e->fd_tmp, head_b + 8 * n + ko_b + s_b + nb + TABLE_SLACK))) return rc;  // (the key bytes are read as table bytes are)
+  const size_t head_b = 16 * n + sizeof(FdCtl), out_b = head_b + (sums ? 8 * n : 0), ko_b = 8 * (n + 1);
+  uint8_t *out, *d_kbytes;
+  uint64_t *d_koffs, *S;
+  if ((rc = carve_dev(e->fd_tmp, [&](Carve& c) {
+         out = c.take_bytes(head_b + 8 * n);
+         d_koffs = c.take<uint64_t>(n + 1);
+         S = c.take<uint64_t>(sums ? ntiles + 1 : 0);
+         d_kbytes = c.take_bytes(nb + TABLE_SLACK);  // (the key bytes are read as table bytes are)
+       })))
+    return rc;
   if ((rc = grow_pinned(e->fd_pin, std::max(out_b, ko_b)))) return rc;
-  uint8_t* p = (uint8_t*)e->fd_tmp.p;
   FdKeys K{};
-  K.first = (uint64_t*)p;
-  K.last = (uint64_t*)(p + 8 * n);
-  K.ctl = (FdCtl*)(p + 16 * n);
-  K.sums = sums ? (uint64_t*)(p + head_b) : nullptr;
-  p += head_b + 8 * n;
-  uint64_t* d_koffs = (uint64_t*)p; p += ko_b;
-  uint64_t* S = (uint64_t*)p; p += s_b;
-  uint8_t* d_kbytes = p;
+  K.first = (uint64_t*)out;
+  K.last = (uint64_t*)(out + 8 * n);
+  K.ctl = (FdCtl*)(out + 16 * n);
+  K.sums = sums ? (uint64_t*)(out + head_b) : nullptr;
   K.koffs = d_koffs;
   K.kbytes = d_kbytes;
   K.nq = n;

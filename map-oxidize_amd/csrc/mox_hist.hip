@@ -274,16 +274,6 @@ extern "C" __global__ __launch_bounds__(HG_T) void k_hg_diff(HgOut O) {
   }
 }
 
-namespace mox_host {
-
-void hist_free(mox_engine* e) {
-  free_bufs({&e->hg_tmp, &e->hg_out});
-  if (e->hg_pin.p) (void)hipHostFree(e->hg_pin.p);
-  e->hg_pin = DevBuf{};
-}
-
-}  // namespace mox_host
-
 namespace {
 
 // The table and its four arrays of n in one host block.
@@ -343,15 +333,15 @@ extern "C" int mox_hist_result(mox_engine* e, const mox_hist* h, mox_hist_table*
   const uint64_t nt = (n + HG_TILE - 1) / HG_TILE;
   const uint32_t grid = (uint32_t)std::min(nt, cap);
   const bool fail_hook = test_fail_hook("MOX_TEST_FAIL_HIST");
-  // scratch: [derived keys n] [tile heads nt + 1] [tile sums nt + 1] (every array a multiple of 256 bytes)
-  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
-  const size_t key_b = h->key == MOX_HIST_COUNT ? 0 : up(8 * n), t_b = up(8 * (nt + 1));
-  if ((rc = grow_dev(e->hg_tmp, key_b + 2 * t_b))) return rc;
+  // scratch: [derived keys n] [tile heads nt + 1] [tile sums nt + 1]
+  uint64_t *d_keys, *th, *tt;
+  if ((rc = carve_dev(e->hg_tmp, [&](Carve& c) {
+         d_keys = c.take<uint64_t>(h->key == MOX_HIST_COUNT ? 0 : n);
+         th = c.take<uint64_t>(nt + 1);
+         tt = c.take<uint64_t>(nt + 1);
+       })))
+    return rc;
   if ((rc = grow_pinned(e->hg_pin, 64))) return rc;
-  uint8_t* p = (uint8_t*)e->hg_tmp.p;
-  uint64_t* d_keys = (uint64_t*)p;
-  uint64_t* th = (uint64_t*)(p + key_b);
-  uint64_t* tt = (uint64_t*)(p + key_b + t_b);
 
   // 1. the keys
   const uint64_t* keys_in = r.counts + first;
@@ -389,10 +379,14 @@ extern "C" int mox_hist_result(mox_engine* e, const mox_hist* h, mox_hist_table*
   if (fail_hook) return fail(MOX_ENOMEM, "hist: injected failure before the bins are written (MOX_TEST_FAIL_HIST)");
 
   // 4. the bins: [keys g] [bin_words g] [bin_tokens g] [first_row g] (what comes back) [positions g + 1] [prefixes g + 1]
-  if ((rc = grow_dev(e->hg_out, up(32 * g) + 2 * up(8 * (g + 1))))) return rc;
-  uint64_t* o = (uint64_t*)e->hg_out.p;
-  uint64_t* d_pos = (uint64_t*)((uint8_t*)o + up(32 * g));
-  const HgOut O{o, o + g, o + 2 * g, o + 3 * g, d_pos, (uint64_t*)((uint8_t*)d_pos + up(8 * (g + 1))), g, first};
+  uint64_t *o, *d_pos, *d_pre;
+  if ((rc = carve_dev(e->hg_out, [&](Carve& c) {
+         o = c.take<uint64_t>(4 * g);
+         d_pos = c.take<uint64_t>(g + 1);
+         d_pre = c.take<uint64_t>(g + 1);
+       })))
+    return rc;
+  const HgOut O{o, o + g, o + 2 * g, o + 3 * g, d_pos, d_pre, g, first};
   mox_hist_table* t = hist_table_new(g);
   if (!t) return fail(MOX_ENOMEM, "hist: host memory for %llu bins", (unsigned long long)g);
   auto drop = [&](int code) {

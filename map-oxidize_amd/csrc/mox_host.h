@@ -6,7 +6,9 @@
 // (mox_lookup.hip), the device filter (mox_filter.hip), the device ranking
 // (mox_rank.hip), the device re-keying (mox_rekey.hip), the device search
 // of the sorted result (mox_find.hip), the device join against the total
-// (mox_join.hip) and the device histograms of the result (mox_hist.hip).  The device-side
+// (mox_join.hip) and the device histograms of the result (mox_hist.hip); the buffers
+// of the calls over the result are grown, laid out and freed in one place
+// (mox_result.hip, mox_carve.h).  The device-side
 // helpers those kernels share are in mox_dev.h and mox_pack.h (the two
 // packers); the host-side ones (result_begin, table_reserve and the
 // declarations around it, Received: the hand-off to the reduce-only pass) are below.
@@ -34,6 +36,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/mox.h"
+#include "mox_carve.h"
 #include "mox_internal.h"
 #include "mox_table.h"
 
@@ -191,7 +194,7 @@ struct mox_engine {
   DevBuf a_tab[3], a_tc;
   DevBuf g_counts, g_offs, g_bytes, g_recv;  // mox_gather (root)
   DevBuf s_counts, s_offs, s_bytes, s_tmp;    // device bytewise sort (mox_bsort.hip): output + scratch
-  unsigned long long* h_bsort = nullptr;      // pinned: the sort's digit histograms + totals
+  DevBuf h_bsort;                             // pinned: the sort's digit histograms + totals
   DevBuf k_tmp, k_out;                        // device top-k (mox_topk.hip): scratch, output block
   // device text rendering (mox_text.hip): scanned tile lengths, two device slices,
   // their pinned host copies and the events "slice copied"
@@ -208,7 +211,7 @@ struct mox_engine {
   // scratch (keys, row indices, digit counts, tile bytes) and the pinned block
   // maxima / totals
   DevBuf r_tab[2][3], r_tmp;
-  uint64_t* h_rmax = nullptr;
+  DevBuf h_rmax;
   // device re-keying (mox_rekey.hip): the packer's tile counts (the wire image
   // goes to x_recv_short / x_recv_blob)
   DevBuf q_tc;
@@ -297,10 +300,20 @@ int stage_host_range(mox_engine* e, const uint8_t* text, size_t len);
 int stage_file_range(mox_engine* e, int fd, uint64_t off, size_t len);
 // MOX_F_SORT_BYTES before a fetch: the implicit device sort (mox_fetch_table, mox_fetch_rows, mox_find_ranges).
 int sort_for_fetch(mox_engine* e, bool* host_sort);
-// ---- mox_multi.hip
+// ---- mox_result.hip
 int grow_dev(DevBuf& b, size_t bytes);
 int grow_pinned(DevBuf& b, size_t bytes);
 void free_bufs(std::initializer_list<DevBuf*> bufs);  // device buffers: freed and reset
+// b grown to hold what layout(Carve&) takes, then laid out by the same calls (mox_carve.h).
+template <class F>
+int carve_dev(DevBuf& b, F&& layout) {
+  Carve size;
+  layout(size);
+  if (int rc = grow_dev(b, size.used)) return rc;
+  Carve place{(uint8_t*)b.p};
+  layout(place);
+  return MOX_OK;
+}
 // The slack every buffer of a result table carries past its contents (mox_dev.h:
 // what the kernels may read past a word because of it).
 constexpr size_t TABLE_SLACK = 64;
@@ -308,12 +321,16 @@ constexpr size_t TABLE_SLACK = 64;
 int table_reserve(DevBuf& counts, DevBuf& offs, DevBuf& bytes, uint64_t n, uint64_t nb);
 // Of two sets of table buffers (counts, offs, bytes), the one the result r does not live in.
 DevBuf* table_other_set(DevBuf (*sets)[3], const mox_engine::Res& r);
-// r's table is the one in set[0..2]; the order and state flags stay the caller's.
+// r's table is the one in set[0..2], an operator's buffers: no pass table and no
+// exchanged one; the order flags and folded stay the caller's.
 void res_point_at(mox_engine::Res& r, DevBuf* set, uint64_t n, uint64_t nb, uint64_t tokens);
 // The grid cap of the kernels over table tiles: 8 workgroups per CU, or fewer with the environment variable env (tests).
 uint64_t grid_cap(const mox_engine* e, const char* env);
 // true when the environment variable env is a non-zero number: a call fails there on purpose (tests).
 bool test_fail_hook(const char* env);
+// Every buffer the calls over the result own (device and pinned), and the text's events.
+void result_free(mox_engine* e);
+// ---- mox_multi.hip
 void group_destroy(mox_engine* e);
 int group_create(mox_engine* e, const mox_config* cfg);
 int group_count_host(mox_engine* e, const uint8_t* text, size_t len);
@@ -336,21 +353,10 @@ mox_stats packed_stats(mox_engine* e, const Received& rx);
 void xplan_free(mox_engine* e);
 // ---- mox_bsort.hip
 int bsort_table(mox_engine* e);  // the result table in bytewise order, on the device
-void bsort_free(mox_engine* e);
-// ---- mox_topk.hip
-void topk_free(mox_engine* e);
-// ---- mox_text.hip
-void text_free(mox_engine* e);
-// ---- mox_accum.hip
-void accum_free(mox_engine* e);
 // ---- mox_lookup.hip
-void lookup_free(mox_engine* e);
 int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uint64_t n, uint64_t* counts, uint64_t* index,
                   mox_lookup_info* info, const uint64_t** d_index);
-// ---- mox_filter.hip
-void filter_free(mox_engine* e);
 // ---- mox_rank.hip
-void rank_free(mox_engine* e);
 // The stable order of n u64 keys on the device (the ranking's radix sort of (key ^ flip,
 // row) pairs over r_tmp).  Valid until the next call that uses r_tmp.
 struct RankOrder {
@@ -363,14 +369,7 @@ struct RankOrder {
 };
 // cap: the grid cap of every launch; extra: bytes of the caller's own scratch in r_tmp.  n >= 1.
 int rank_order(mox_engine* e, const uint64_t* d_keys, uint64_t n, uint64_t flip, uint64_t cap, size_t extra, RankOrder* out);
-// ---- mox_hist.hip
-void hist_free(mox_engine* e);
-// ---- mox_rekey.hip
-void rekey_free(mox_engine* e);
-// ---- mox_find.hip
-void find_free(mox_engine* e);
 // ---- mox_join.hip
-void join_free(mox_engine* e);
 // Sums over the rows of the result whose word the other table holds.
 struct JoinSums {
   uint64_t matched = 0, tokens_result = 0, tokens_total = 0, tokens_min = 0, tag_mismatch = 0;

@@ -389,8 +389,6 @@ extern "C" __global__ __launch_bounds__(JN_T) void k_jn_apply(JnSet S, uint32_t 
 
 namespace mox_host {
 
-void join_free(mox_engine* e) { free_bufs({&e->j_tmp}); }
-
 // The match of mox_join_total (mox_filter.hip): bit j of matched (r.n bits,
 // zeroed by the caller, in device memory) is set where the table t holds the
 // word of r's row j; *sums are the sums over those rows.  With counts_mode
@@ -404,18 +402,20 @@ int join_match(mox_engine* e, const mox_engine::Res& r, const uint64_t* t_counts
   const bool sub = counts_mode != MOX_JOIN_COUNTS_RESULT;
   // device scratch: [control block | slots] (zeroed together) | jc | substituted counts
   const uint64_t nslots = std::max<uint64_t>(JN_MIN_SLOTS, next_pow2(JN_SLOTS_PER_ROW * r.n));
-  const size_t sl_b = 8 * nslots, jc_b = 8 * r.n;
-  if (int rc = grow_dev(e->j_tmp, sizeof(JnCtl) + sl_b + jc_b * (sub ? 2 : 1))) return rc;
-  uint8_t* p = (uint8_t*)e->j_tmp.p;
+  const size_t sl_b = 8 * nslots;
   JnSet S{};
+  uint64_t* d_subst;
+  if (int rc = carve_dev(e->j_tmp, [&](Carve& c) {
+        S.ctl = (JnCtl*)c.take_bytes(sizeof(JnCtl) + sl_b);
+        S.jc = c.take<uint64_t>(r.n);
+        d_subst = sub ? c.take<uint64_t>(r.n) : nullptr;
+      }))
+    return rc;
   S.R = JnTab{r.counts, r.offs, r.bytes, r.n};
-  S.ctl = (JnCtl*)p;
-  S.slots = (unsigned long long*)(p + sizeof(JnCtl));
+  S.slots = (unsigned long long*)(S.ctl + 1);
   S.mask = nslots - 1;
-  S.jc = (uint64_t*)(p + sizeof(JnCtl) + sl_b);
   S.matched = matched;
-  uint64_t* d_subst = sub ? S.jc + r.n : nullptr;
-  HIPCHK(hipMemsetAsync(p, 0, sizeof(JnCtl) + sl_b, st));
+  HIPCHK(hipMemsetAsync(S.ctl, 0, sizeof(JnCtl) + sl_b, st));
   const uint64_t rtiles = (r.n + JN_TILE - 1) / JN_TILE, ttiles = (t_n + JN_TILE - 1) / JN_TILE;
   hipLaunchKernelGGL(k_jn_build, dim3((uint32_t)std::min(rtiles, cap)), dim3(JN_T), 0, st, S);
   q.step("k_jn_build");

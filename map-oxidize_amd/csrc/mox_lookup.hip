@@ -398,12 +398,6 @@ extern "C" __global__ __launch_bounds__(LK_T) void k_lk_finish(LkSet S) {
 
 namespace mox_host {
 
-void lookup_free(mox_engine* e) {
-  free_bufs({&e->l_tmp});
-  if (e->l_pin.p) (void)hipHostFree(e->l_pin.p);
-  e->l_pin = DevBuf{};
-}
-
 // mox_lookup_words; with d_index (mox_filter.hip) counts may be NULL, and
 // *d_index is the index array in device memory (n entries in l_tmp, valid until
 // the next lookup; NULL for n == 0): then only the control block comes back.
@@ -432,19 +426,22 @@ int lookup_device(mox_engine* e, const uint8_t* bytes, const uint64_t* offs, uin
   int rc;
   // device scratch: [counts n | control block | index n] (the part that comes back) | rep | query offsets | slots | query bytes
   const uint64_t nslots = std::max<uint64_t>(LK_MIN_SLOTS, next_pow2(LK_SLOTS_PER_QUERY * n));
-  const size_t out_b = 16 * n + sizeof(LkCtl), rep_b = (4 * n + 7) & ~(size_t)7, qo_b = 8 * (n + 1), sl_b = 8 * nslots;
-  if ((rc = grow_dev(e->l_tmp, out_b + rep_b + qo_b + sl_b + nb + TABLE_SLACK))) return rc;  // (the query bytes are read as table bytes are)
-  if ((rc = grow_pinned(e->l_pin, std::max(out_b, qo_b)))) return rc;
-  uint8_t* p = (uint8_t*)e->l_tmp.p;
+  const size_t out_b = 16 * n + sizeof(LkCtl), qo_b = 8 * (n + 1), sl_b = 8 * nslots;
   LkSet S{};
-  S.o_counts = (uint64_t*)p;
-  S.ctl = (LkCtl*)(p + 8 * n);
-  S.o_index = (uint64_t*)(p + 8 * n + sizeof(LkCtl));
-  p += out_b;
-  S.rep = (uint32_t*)p; p += rep_b;
-  uint64_t* d_qoffs = (uint64_t*)p; p += qo_b;
-  S.slots = (unsigned long long*)p; p += sl_b;
-  uint8_t* d_qbytes = p;
+  uint8_t *out, *d_qbytes;
+  uint64_t* d_qoffs;
+  if ((rc = carve_dev(e->l_tmp, [&](Carve& c) {
+         out = c.take_bytes(out_b);
+         S.rep = c.take<uint32_t>(n);
+         d_qoffs = c.take<uint64_t>(n + 1);
+         S.slots = c.take<unsigned long long>(nslots);
+         d_qbytes = c.take_bytes(nb + TABLE_SLACK);  // (the query bytes are read as table bytes are)
+       })))
+    return rc;
+  if ((rc = grow_pinned(e->l_pin, std::max(out_b, qo_b)))) return rc;
+  S.o_counts = (uint64_t*)out;
+  S.ctl = (LkCtl*)(out + 8 * n);
+  S.o_index = (uint64_t*)(out + 8 * n + sizeof(LkCtl));
   S.qoffs = d_qoffs;
   S.qbytes = d_qbytes;
   S.nq = n;

@@ -23,66 +23,6 @@ namespace mox_host {
 // then one reduce-only pass over the received partials produces this rank's
 // final table.  Ranks own disjoint word sets.
 
-int grow_dev(DevBuf& b, size_t bytes) {
-  if (b.cap >= bytes && b.p) return MOX_OK;
-  dfree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-  hipError_t err = hipMalloc(&b.p, want);
-  if (err != hipSuccess) {
-    b.p = nullptr;
-    (void)hipGetLastError();  // the failed allocation's error is not a later launch's (callers may fall back)
-    return fail(MOX_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(err));
-  }
-  b.cap = want;
-  return MOX_OK;
-}
-int grow_pinned(DevBuf& b, size_t bytes) {
-  if (b.cap >= bytes && b.p) return MOX_OK;
-  if (b.p) (void)hipHostFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-  hipError_t err = hipHostMalloc(&b.p, want, hipHostMallocDefault);
-  if (err != hipSuccess) return fail(MOX_ENOMEM, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(err));
-  b.cap = want;
-  return MOX_OK;
-}
-void free_bufs(std::initializer_list<DevBuf*> bufs) {
-  for (DevBuf* b : bufs) {
-    dfree(b->p);
-    *b = DevBuf{};
-  }
-}
-int table_reserve(DevBuf& counts, DevBuf& offs, DevBuf& bytes, uint64_t n, uint64_t nb) {
-  int rc;
-  if ((rc = grow_dev(counts, 8 * n + TABLE_SLACK)) || (rc = grow_dev(offs, 8 * (n + 1) + TABLE_SLACK)) || (rc = grow_dev(bytes, nb + TABLE_SLACK)))
-    return rc;
-  return MOX_OK;
-}
-DevBuf* table_other_set(DevBuf (*sets)[3], const mox_engine::Res& r) {
-  return sets[(sets[0][0].p && r.counts == (const uint64_t*)sets[0][0].p) ? 1 : 0];
-}
-void res_point_at(mox_engine::Res& r, DevBuf* set, uint64_t n, uint64_t nb, uint64_t tokens) {
-  r.counts = (const uint64_t*)set[0].p;
-  r.offs = (const uint64_t*)set[1].p;
-  r.bytes = (const uint8_t*)set[2].p;
-  r.n = n;
-  r.nb = nb;
-  r.tokens = tokens;
-}
-uint64_t grid_cap(const mox_engine* e, const char* env) {
-  uint64_t cap = 8ull * (uint64_t)e->n_cu;
-  if (const char* g = getenv(env))
-    if (atoll(g) > 0) cap = std::min<uint64_t>(cap, (uint64_t)atoll(g));
-  return cap;
-}
-bool test_fail_hook(const char* env) {
-  const char* x = getenv(env);
-  return x && atoi(x);
-}
-
 // Moves per-peer byte ranges between ranks.  send/recv are device buffers;
 // off/len are per-peer byte offsets and sizes (len identical on both sides of
 // every pair by construction).

@@ -377,12 +377,6 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_emit(RkTab T, RkOrder O,
 
 namespace mox_host {
 
-void rank_free(mox_engine* e) {
-  free_bufs({&e->r_tab[0][0], &e->r_tab[0][1], &e->r_tab[0][2], &e->r_tab[1][0], &e->r_tab[1][1], &e->r_tab[1][2], &e->r_tmp});
-  if (e->h_rmax) (void)hipHostFree(e->h_rmax);
-  e->h_rmax = nullptr;
-}
-
 // The stable order of n u64 keys on the device by key ^ flip (steps 1 and 2 of
 // the file's header): the ranking's, and the histogram's over its own keys.
 // extra: bytes of the caller's own scratch, carved behind the sort's in r_tmp.
@@ -393,27 +387,29 @@ int rank_order(mox_engine* e, const uint64_t* d_keys, uint64_t n, uint64_t flip,
   const uint64_t nt = (n + RK_TILE - 1) / RK_TILE;
   const uint32_t grid = (uint32_t)std::min(nt, cap);
   // scratch: [block maxima] [keys A] [keys B] [rows A] [rows B] [digit counts 256 nt] [chunk sums nc + 1] [the caller's extra bytes]
-  // (every array a multiple of 256 bytes)
   const uint64_t m = (uint64_t)RK_DIGITS * nt, nc = (m + RK_CHUNK - 1) / RK_CHUNK;
-  auto up = [](uint64_t b) { return (b + 255) & ~255ull; };
-  const size_t bm_b = up(8 * cap), key_b = up(8 * n), idx_b = up(4 * n), th_b = up(4 * m), cs_b = up(4 * (nc + 1)), tb_b = up(extra);
-  if ((rc = grow_dev(e->r_tmp, bm_b + 2 * key_b + 2 * idx_b + th_b + cs_b + tb_b))) return rc;
-  if (!e->h_rmax) HIPCHK(hipHostMalloc((void**)&e->h_rmax, 8 * (8 * (size_t)e->n_cu + 8), hipHostMallocDefault));
-  uint8_t* p = (uint8_t*)e->r_tmp.p;
-  uint64_t* bm = (uint64_t*)p;
-  uint64_t* keys[2] = {(uint64_t*)(p + bm_b), (uint64_t*)(p + bm_b + key_b)};
-  uint32_t* rows[2] = {(uint32_t*)(p + bm_b + 2 * key_b), (uint32_t*)(p + bm_b + 2 * key_b + idx_b)};
-  uint32_t* th = (uint32_t*)(p + bm_b + 2 * key_b + 2 * idx_b);
-  uint32_t* cs = (uint32_t*)((uint8_t*)th + th_b);
+  uint64_t *bm, *keys[2];
+  uint32_t *rows[2], *th, *cs;
+  if ((rc = carve_dev(e->r_tmp, [&](Carve& c) {
+         bm = c.take<uint64_t>(cap);
+         for (auto& k : keys) k = c.take<uint64_t>(n);
+         for (auto& r : rows) r = c.take<uint32_t>(n);
+         th = c.take<uint32_t>(m);
+         cs = c.take<uint32_t>(nc + 1);
+         out->extra = c.take_bytes(extra);
+       })))
+    return rc;
+  if ((rc = grow_pinned(e->h_rmax, 8 * (8 * (size_t)e->n_cu + 8)))) return rc;
+  uint64_t* h_max = (uint64_t*)e->h_rmax.p;
 
   // 1. the largest key and the digits it has
   hipLaunchKernelGGL(k_rk_max, dim3(grid), dim3(RK_T), 0, st, d_keys, n, bm);
   q.step("k_rk_max");
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(e->h_rmax, bm, 8 * (size_t)grid, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(h_max, bm, 8 * (size_t)grid, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   uint64_t max_key = 0;
-  for (uint32_t g = 0; g < grid; g++) max_key = std::max<uint64_t>(max_key, e->h_rmax[g]);
+  for (uint32_t g = 0; g < grid; g++) max_key = std::max<uint64_t>(max_key, h_max[g]);
   uint32_t passes = 0;
   while (passes < 8 && (max_key >> (8 * passes))) passes++;
 
@@ -439,7 +435,6 @@ int rank_order(mox_engine* e, const uint64_t* d_keys, uint64_t n, uint64_t flip,
   out->max_key = max_key;
   out->passes = passes;
   out->d_counted = passes ? cs + nc : nullptr;
-  out->extra = (uint8_t*)cs + cs_b;
   return MOX_OK;
 }
 
@@ -497,7 +492,7 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
   hipLaunchKernelGGL(k_rk_offs, dim3(1), dim3(RK_TOP_T), 0, st, tb, T.nt);
   q.step("k_rk_offs");
   HIPCHK(hipGetLastError());
-  uint64_t* h_tot = e->h_rmax;  // the rows the last pass counted (a u32: the low half of a zeroed word), the bytes of the new order
+  uint64_t* h_tot = (uint64_t*)e->h_rmax.p;  // the rows the last pass counted (a u32: the low half of a zeroed word), the bytes of the new order
   h_tot[0] = h_tot[1] = 0;
   if (passes) HIPCHK(hipMemcpyAsync(h_tot, ro.d_counted, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(h_tot + 1, tb + T.nt, 8, hipMemcpyDeviceToHost, st));
@@ -518,8 +513,6 @@ extern "C" int mox_rank_result(mox_engine* e, uint32_t flags, mox_rank_info* inf
   // the same words and counts in the new order: tokens, n, the bytes and folded are the source's
   mox_engine::Res& res = e->res;
   res_point_at(res, dst, r.n, r.nb, r.tokens);
-  res.pass = false;
-  res.exchanged = false;
   res.sorted = false;
   res.ranked = true;
   return finish();

@@ -320,14 +320,6 @@ extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(RqTab T, RqSpec 
   }
 }
 
-namespace mox_host {
-
-void rekey_free(mox_engine* e) {
-  free_bufs({&e->q_tc});
-}
-
-}  // namespace mox_host
-
 extern "C" int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_info* info) {
   if (!e) return fail(MOX_EINVAL, "engine is NULL");
   if (!k) return fail(MOX_EINVAL, "rekey: the spec is NULL");

@@ -294,23 +294,6 @@ extern "C" __global__ __launch_bounds__(TX_T) void k_tx_emit(const uint64_t* __r
   }
 }
 
-namespace mox_host {
-
-void text_free(mox_engine* e) {
-  free_bufs({&e->tx_pre, &e->tx_slice[0], &e->tx_slice[1]});
-  for (DevBuf& b : e->tx_pin) {
-    if (b.p) (void)hipHostFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-  }
-  for (hipEvent_t& ev : e->tx_ev) {
-    if (ev) (void)hipEventDestroy(ev);
-    ev = nullptr;
-  }
-}
-
-}  // namespace mox_host
-
 namespace {
 
 // Where the text goes: a file (pwrite at the slice's offset) or host memory.

@@ -301,14 +301,6 @@ extern "C" __global__ __launch_bounds__(256) void k_tk_gather(uint64_t kk, const
   for (uint64_t b = (uint64_t)blockIdx.y * 256 + threadIdx.x; b < len; b += (uint64_t)gridDim.y * 256) ob[dst + b] = bytes[src + b];
 }
 
-namespace mox_host {
-
-void topk_free(mox_engine* e) {
-  free_bufs({&e->k_tmp, &e->k_out});
-}
-
-}  // namespace mox_host
-
 // The top-k of n rows of the result (a result is open: result_begin): row i's
 // count is r_counts[i] and its word bytes[r_offs[i], r_offs[i + 1]) of the
 // result's bytes, so a row range of the table is the table's two arrays from
@@ -323,17 +315,21 @@ static int top_of_rows(mox_engine* e, const uint64_t* r_counts, const uint64_t* 
   uint64_t nb = 0;
   if (kk) {
     const uint64_t ntiles = (n + TK_TILE - 1) / TK_TILE;
-    // scratch: control block | histograms | candidates | counts, source offsets, offsets | tile counts + total
-    const size_t hist_b = (size_t)TK_LEVELS * TK_BINS * 8, cand_b = (size_t)TK_MAX * sizeof(TkCand), arr_b = ((size_t)TK_MAX + 1) * 8;
-    if (int rc = grow_dev(e->k_tmp, sizeof(TkCtl) + hist_b + cand_b + 3 * arr_b + (ntiles + 1) * 8)) return rc;
-    uint8_t* p = (uint8_t*)e->k_tmp.p;
-    TkCtl* ctl = (TkCtl*)p; p += sizeof(TkCtl);
-    unsigned long long* hist = (unsigned long long*)p; p += hist_b;
-    TkCand* cand = (TkCand*)p; p += cand_b;
-    uint64_t* o_counts = (uint64_t*)p; p += arr_b;
-    uint64_t* o_src = (uint64_t*)p; p += arr_b;
-    uint64_t* o_offs = (uint64_t*)p; p += arr_b;
-    uint64_t* tcnt = (uint64_t*)p;
+    // scratch: [control block | histograms] (zeroed together) | candidates | counts, source offsets, offsets | tile counts + total
+    const size_t hist_b = (size_t)TK_LEVELS * TK_BINS * 8;
+    TkCtl* ctl;
+    TkCand* cand;
+    uint64_t *o_counts, *o_src, *o_offs, *tcnt;
+    if (int rc = carve_dev(e->k_tmp, [&](Carve& c) {
+          ctl = (TkCtl*)c.take_bytes(sizeof(TkCtl) + hist_b);
+          cand = c.take<TkCand>(TK_MAX);
+          o_counts = c.take<uint64_t>((size_t)TK_MAX + 1);
+          o_src = c.take<uint64_t>((size_t)TK_MAX + 1);
+          o_offs = c.take<uint64_t>((size_t)TK_MAX + 1);
+          tcnt = c.take<uint64_t>(ntiles + 1);
+        }))
+      return rc;
+    unsigned long long* hist = (unsigned long long*)(ctl + 1);
     HIPCHK(hipMemsetAsync(ctl, 0, sizeof(TkCtl) + hist_b, st));
     // k_tk_hist: a workgroup's LDS bins are 32-bit, so its share of the counts stays below 2^32
     const uint64_t hgrid = std::max<uint64_t>(std::min<uint64_t>((n + TK_T * TK_HIST_PER - 1) / (TK_T * TK_HIST_PER), 8ull * e->n_cu),

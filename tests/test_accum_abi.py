@@ -11,16 +11,13 @@ import pytest
 import accum_cases as C
 import mox
 from conftest import ROOT
+from srcpins import code_only
 
 FUNCS = ["mox_accumulate", "mox_accumulate_file", "mox_accumulate_reset", "mox_accumulate_info"]
 
 
 def header():
     return open(os.path.join(ROOT, "include", "mox.h")).read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
 
 
 def test_header_declares_the_accumulator():

@@ -11,29 +11,7 @@ import pytest
 import filter_cases as C
 import mox
 from conftest import ROOT
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-
-
-def struct_fields(src, name):
-    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src)
-    assert m, name
-    out = []
-    for decl in m.group(1).split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        typ, rest = re.match(r"((?:const )?[a-z0-9_]+\*?) (.*)", decl).groups()
-        for field in rest.split(","):
-            out.append((typ, field.strip()))
-    return out
+from srcpins import _read, code_only, op_objects, struct_fields
 
 
 def test_header_declares_the_filter():
@@ -126,10 +104,7 @@ def test_constants_match_the_source():
         assert re.search(r'extern "C" __global__ .* void %s\(' % k, src) and 'q.step("%s")' % k in src, k
     # the LDS list of long words and list_found only: no global atomic places a row
     assert set(re.findall(r"atomicAdd\(&?(\w+)", src)) == {"s_nf", "found", "s_nbig"}
-    mk = _read("Makefile")
-    assert mk.count("$(OUT)/mox_filter.o") >= 4 and "mox_filter_hc.o" not in mk
-    for lib in ("libmox.so", "libmox_check.so", "libmox_hc.so"):
-        assert re.search(r"^\$\(OUT\)/%s:.*\$\(OUT\)/mox_filter\.o" % re.escape(lib), mk, re.M), lib
+    op_objects("filter", hc=False)  # no mox_filter_hc.o: the plain object in all three libraries
 
 
 def test_expected_on_hand_written_cases():

@@ -15,16 +15,8 @@ import pytest
 import find_cases as C
 import mox
 from conftest import ROOT
+from srcpins import _read, code_only, op_objects
 from mox import dist
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
 
 
 KERNELS = ("k_fd_search", "k_fd_tiles", "k_fd_scan", "k_fd_sum")
@@ -186,21 +178,17 @@ def test_constants_and_kernels_match_the_source():
     assert set(re.findall(r"\b(k_fd_\w+)\(", src)) == set(KERNELS)
     # no atomic touches a count or an output: the error word only; and no workgroup waits on another
     assert set(re.findall(r"atomic\w+\(&?([\w.>-]+)", src)) == {"K.ctl->err"}
-    assert not re.search(r"\bwhile\b|s_sleep|__threadfence|volatile", src.split("namespace mox_host")[0])
+    assert not re.search(r"\bwhile\b|s_sleep|__threadfence|volatile", src.split('extern "C" int mox_find_ranges(')[0])  # (the kernels: the host side starts there)
     assert 'grid_cap(e, "MOX_FIND_GRID")' in src and "sort_for_fetch(e, &host_sort)" in src
     report = src.split("#include")[0].split("Resource usage")[1]
     for k in KERNELS:
         assert re.search(r"%s\s+\d+ VGPRs, \d+ SGPRs,\s+\d+ B LDS, no scratch, no spills" % k, report), k
-    mk = _read("Makefile")
-    assert "mox_find_hc.o" not in mk and "mox_find_check.o" not in mk
-    assert re.search(r"^\$\(OUT\)/mox_find\.o: .*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) \$\(KERNEL_FLAGS\) -c", mk, re.M)
-    for lib in ("libmox.so", "libmox_check.so", "libmox_hc.so"):
-        assert re.search(r"^\$\(OUT\)/%s:.*\$\(OUT\)/mox_find\.o" % re.escape(lib), mk, re.M), lib
+    op_objects("find", hc=False)  # no mox_find_hc.o, no mox_find_check.o; KERNEL_FLAGS; once per library
     host = _read("map-oxidize_amd", "csrc", "mox_host.h")
-    assert "DevBuf fd_tmp, fd_pin;" in host and "void find_free(mox_engine* e);" in host
+    assert "DevBuf fd_tmp, fd_pin;" in host  # (freed: test_result_buffers.py)
     assert "int sort_for_fetch(mox_engine* e, bool* host_sort);" in host  # exposed, not copied
     engine = _read("map-oxidize_amd", "csrc", "mox_engine.hip")
-    assert "find_free(e);" in engine and len(re.findall(r"^int sort_for_fetch\(", engine, re.M)) == 1
+    assert len(re.findall(r"^int sort_for_fetch\(", engine, re.M)) == 1
     # mox_top_words and mox_top_rows share one body
     topk = _read("map-oxidize_amd", "csrc", "mox_topk.hip")
     assert topk.count("top_of_rows(e, ") == 2 and topk.count("k_tk_sort, dim3(1)") == 1

@@ -15,16 +15,8 @@ import hist_cases as C
 import mox
 import rank_cases
 from conftest import ROOT
+from srcpins import _read, code_only, op_objects
 from mox import dist
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
 
 
 KERNELS = ("k_hg_keys", "k_hg_count", "k_hg_scan", "k_hg_bins", "k_hg_diff")
@@ -152,7 +144,7 @@ def test_constants_and_kernels_match_the_source():
         assert re.search(r'extern "C" __global__ .* void %s\(' % k, src) and 'q.step("%s")' % k in src, k
     assert set(re.findall(r"\b(k_hg_\w+)\(", src)) == set(KERNELS)
     # the LDS list of long words only: no global atomic places a bin or adds a count; and no workgroup waits on another
-    device = src.split("namespace mox_host")[0]
+    device = src.split('extern "C" void mox_hist_free(')[0]  # (the kernels: the entry points start there)
     assert set(re.findall(r"atomic\w+\(&?([\w.>-]+)", src)) == {"s_nbig"} and "__shared__ uint32_t s_nbig;" in device
     assert not re.search(r"\bwhile\b|s_sleep|__threadfence|volatile", device)
     assert 'grid_cap(e, "MOX_HIST_GRID")' in src and 'test_fail_hook("MOX_TEST_FAIL_HIST")' in src
@@ -172,19 +164,13 @@ def test_the_ranking_shares_its_sort_and_keeps_its_kernels():
     host = _read("map-oxidize_amd", "csrc", "mox_host.h")
     assert ("int rank_order(mox_engine* e, const uint64_t* d_keys, uint64_t n, uint64_t flip, uint64_t cap, size_t extra, "
             "RankOrder* out);") in host
-    assert "struct RankOrder {" in host and "DevBuf hg_tmp, hg_out, hg_pin;" in host and "void hist_free(mox_engine* e);" in host
-    assert "hist_free(e);" in _read("map-oxidize_amd", "csrc", "mox_engine.hip")
+    assert "struct RankOrder {" in host and "DevBuf hg_tmp, hg_out, hg_pin;" in host  # (freed: test_result_buffers.py)
     for name in ("mox_dev.h", "mox_host.h"):
         assert "mox_hist.hip" in _read("map-oxidize_amd", "csrc", name).split("#pragma once")[0], name
 
 
 def test_makefile_puts_one_object_into_all_three_libraries():
-    mk = _read("Makefile")
-    assert "mox_hist_hc.o" not in mk and "mox_hist_check.o" not in mk
-    assert re.search(r"^\$\(OUT\)/mox_hist\.o: .*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) \$\(KERNEL_FLAGS\) -c", mk, re.M)
-    for lib in ("libmox.so", "libmox_check.so", "libmox_hc.so"):
-        line = re.search(r"^\$\(OUT\)/%s:(.*)$" % re.escape(lib), mk, re.M).group(1)
-        assert line.split().count("$(OUT)/mox_hist.o") == 1, lib
+    op_objects("hist", hc=False)  # no mox_hist_hc.o, no mox_hist_check.o; KERNEL_FLAGS; once per library
 
 
 def test_keys_on_hand_written_words():

@@ -12,32 +12,10 @@ import pytest
 import join_cases as C
 import mox
 from conftest import ROOT
+from srcpins import _read, code_only, op_objects, struct_fields
 from mox import dist
 
 CLI = os.path.join(ROOT, "map-oxidize_amd", "mox", "meduce-gpu")
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-
-
-def struct_fields(src, name):
-    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src)
-    assert m, name
-    out = []
-    for decl in m.group(1).split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        typ, rest = re.match(r"((?:const )?[a-z0-9_]+\*?) (.*)", decl).groups()
-        for field in rest.split(","):
-            out.append((typ, field.strip()))
-    return out
 
 
 def test_header_declares_the_join():
@@ -161,17 +139,12 @@ def test_constants_match_the_source():
     assert 'extern "C" int mox_join_total(' in flt and "k_fl_" not in re.sub(r"//.*", "", src)  # no second compaction
     for name in ("mox_dev.h", "mox_host.h"):
         assert "mox_join.hip" in _read("map-oxidize_amd", "csrc", name).split("#pragma once")[0], name
-    assert "join_free(e);" in _read("map-oxidize_amd", "csrc", "mox_engine.hip")
+    assert "DevBuf j_tmp;" in _read("map-oxidize_amd", "csrc", "mox_host.h")  # (freed: test_result_buffers.py)
 
 
 def test_makefile_links_the_join():
-    mk = _read("Makefile")
-    for lib, obj in (("libmox.so", "mox_join.o"), ("libmox_check.so", "mox_join.o"), ("libmox_hc.so", "mox_join_hc.o")):
-        line = re.search(r"^\$\(OUT\)/%s:(.*)$" % re.escape(lib), mk, re.M).group(1)
-        assert "$(OUT)/%s" % obj in line.split(), (lib, obj)
-    hc = re.search(r"^\$\(OUT\)/mox_join_hc\.o:.*\n\t(.*)$", mk, re.M).group(1)
-    assert "$(HC_FLAGS)" in hc and "$(KERNEL_FLAGS)" in hc
-    assert "mox_wordhash.h" in re.search(r"^HOST_DEPS := (.*)$", mk, re.M).group(1)
+    op_objects("join", hc=True)  # mox_join_hc.o (KERNEL_FLAGS and HC_FLAGS) in libmox_hc.so, mox_join.o in the two others
+    assert "mox_wordhash.h" in re.search(r"^HOST_DEPS := (.*)$", _read("Makefile"), re.M).group(1)
 
 
 def test_expected_on_hand_written_cases():

@@ -12,15 +12,7 @@ import lookup_cases as C
 import mox
 from mox import dist as mdist
 from conftest import ROOT
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+from srcpins import _read, code_only, op_objects
 
 
 def test_header_declares_the_lookup():
@@ -82,9 +74,7 @@ def test_constants_match_the_source():
     assert int(re.search(r"^constexpr int LK_TAG_BITS = (\d+);", src, re.M).group(1)) == C.TAG_BITS
     assert C.IDX_BITS + C.TAG_BITS == 64 and C.LOOKUP_MAX + 1 < 1 << C.IDX_BITS  # index + 1 fits its field
     assert "fnv_finish" in src  # the forced-collision build truncates the hash
-    mk = _read("Makefile")
-    assert mk.count("$(OUT)/mox_lookup.o") >= 3 and "$(OUT)/mox_lookup_hc.o: " in mk
-    assert re.search(r"mox_lookup_hc\.o:.*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) \$\(KERNEL_FLAGS\) \$\(HC_FLAGS\)", mk)
+    op_objects("lookup", hc=True)  # mox_lookup_hc.o (KERNEL_FLAGS and HC_FLAGS) in libmox_hc.so, mox_lookup.o in the two others
 
 
 def test_sum_lookups():

@@ -13,29 +13,7 @@ import pytest
 import mox
 import rank_cases as C
 from conftest import ROOT
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
-
-
-def code_only(src):
-    return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-
-
-def struct_fields(src, name):
-    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src)
-    assert m, name
-    out = []
-    for decl in m.group(1).split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        typ, rest = re.match(r"((?:const )?[a-z0-9_]+\*?) (.*)", decl).groups()
-        for field in rest.split(","):
-            out.append((typ, field.strip()))
-    return out
+from srcpins import _read, code_only, op_objects, struct_fields
 
 
 KERNELS = ("k_rk_max", "k_rk_hist", "k_rk_scan_part", "k_rk_scan_top", "k_rk_scan_apply", "k_rk_scatter", "k_rk_len", "k_rk_offs",
@@ -138,13 +116,9 @@ def test_constants_and_kernels_match_the_source():
     report = src.split("#include")[0].split("Resource usage")[1]
     for k in KERNELS:
         assert re.search(r"%s\s+\d+ VGPRs, \d+ SGPRs,\s+\d+ B LDS, no scratch, no spills" % k, report), k
-    mk = _read("Makefile")
-    assert mk.count("$(OUT)/mox_rank.o") >= 4 and "mox_rank_hc.o" not in mk and "mox_rank_check.o" not in mk
-    for lib in ("libmox.so", "libmox_check.so", "libmox_hc.so"):
-        assert re.search(r"^\$\(OUT\)/%s:.*\$\(OUT\)/mox_rank\.o" % re.escape(lib), mk, re.M), lib
+    op_objects("rank", hc=False)  # one object, with KERNEL_FLAGS, once in each of the three libraries
     host = _read("map-oxidize_amd", "csrc", "mox_host.h")
-    assert "DevBuf r_tab[2][3], r_tmp;" in host and "bool ranked = false;" in host and "void rank_free(mox_engine* e);" in host
-    assert "rank_free(e);" in _read("map-oxidize_amd", "csrc", "mox_engine.hip")
+    assert "DevBuf r_tab[2][3], r_tmp;" in host and "bool ranked = false;" in host  # (freed: test_result_buffers.py)
 
 
 def test_ranked_is_treated_wherever_sorted_is_written():

@@ -13,7 +13,7 @@ import pytest
 import mox
 import rekey_cases as C
 from conftest import ROOT
-from test_rank_abi import _read, code_only, struct_fields
+from srcpins import _read, code_only, op_objects, struct_fields
 
 KERNELS = ("k_rekey_count", "k_rekey_scan", "k_rekey_pack")
 
@@ -135,7 +135,7 @@ def test_constants_and_kernels_match_the_source():
     assert set(re.findall(r"\b(k_rekey_\w+)\(", src)) == set(KERNELS)
     # the LDS list of long words only: no atomic, global or not, places a record; and no workgroup waits on another
     assert set(re.findall(r"atomic\w+\(&?(\w+)", src)) == {"s_nbig"}
-    assert not re.search(r"\bwhile\b|s_sleep|__threadfence|volatile", src.split("namespace mox_host")[0].split("#include", 1)[1])
+    assert not re.search(r"\bwhile\b|s_sleep|__threadfence|volatile", src.split('extern "C" int mox_rekey_result(')[0].split("#include", 1)[1])
     assert "fnv_finish(h)" in src and "reduce_received(" in src and "k_reduce_z" in src
     # the header comment carries the compiler's resource report of every kernel, the slack argument and the serial walk
     head = src.split("#include")[0]
@@ -144,13 +144,8 @@ def test_constants_and_kernels_match_the_source():
         assert re.search(r"%s\s+\d+ VGPRs,\s+\d+ SGPRs,\s+\d+ B LDS, no scratch, no spills" % k, report), k
     for phrase in ("slack contract", "never reads before the word's first", "100,000 steps", "mox_accum.hip is untouched"):
         assert phrase in re.sub(r"\n// ?", " ", head), phrase
-    mk = _read("Makefile")
-    for lib, obj in (("libmox.so", "mox_rekey.o"), ("libmox_check.so", "mox_rekey.o"), ("libmox_hc.so", "mox_rekey_hc.o")):
-        assert re.search(r"^\$\(OUT\)/%s:.*\$\(OUT\)/%s" % (re.escape(lib), re.escape(obj)), mk, re.M), lib
-    assert re.search(r"^\$\(OUT\)/mox_rekey_hc\.o:.*\n\t.*\$\(HC_FLAGS\)", mk, re.M)
-    host = _read("map-oxidize_amd", "csrc", "mox_host.h")
-    assert "DevBuf q_tc;" in host and "void rekey_free(mox_engine* e);" in host
-    assert "rekey_free(e);" in _read("map-oxidize_amd", "csrc", "mox_engine.hip")
+    op_objects("rekey", hc=True)  # mox_rekey_hc.o (HC_FLAGS) in libmox_hc.so, mox_rekey.o in the two others
+    assert "DevBuf q_tc;" in _read("map-oxidize_amd", "csrc", "mox_host.h")  # (freed: test_result_buffers.py)
 
 
 def test_model_on_hand_written_cases():

@@ -10,12 +10,8 @@ import pytest
 import mox
 from mox import dist as mdist
 from conftest import ROOT
+from srcpins import _read
 import top_cases as C
-
-
-def _read(*parts):
-    with open(os.path.join(ROOT, *parts)) as f:
-        return f.read()
 
 
 def test_header_declares_top_words():
