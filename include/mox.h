@@ -233,7 +233,12 @@ int mox_fetch_table(mox_engine* e, mox_table** out);
  * Ord) on the GPU, without fetching it (e.g. the root's table after
  * mox_gather, inside a timed multi-GPU step).  MOX_ENOMEM when the sort's
  * device scratch cannot be allocated: the table then stays in engine order
- * (mox_fetch_table with MOX_F_SORT_BYTES still sorts it, on the host). */
+ * (mox_fetch_table with MOX_F_SORT_BYTES still sorts it, on the host).
+ * State: the result is marked sorted and a ranking (mox_rank_result) ends;
+ * tokens, the folded state and the accumulator are unchanged.  A result that
+ * is sorted already is not sorted again: only its ranked mark goes.  A table of at most one word is in every order: nothing moves, it
+ * stays in the buffers it was in, and mox_find_ranges takes it whether it was
+ * ever sorted or not. */
 int mox_sort_result(mox_engine* e);
 /* The k most frequent words of the device-resident result (after any run,
  * mox_reduce_pairs, mox_exchange, mox_gather, mox_run_shards, mox_sort_result),
@@ -307,7 +312,12 @@ void mox_text_free(uint8_t* text);
  * later run; only the result is replaced by them.  On any error the accumulator
  * is what it was before the call, the engine's result becomes that previous
  * total (with an empty accumulator it is left as it was) and the run's
- * contribution is lost: run it again and fold again.  A merge reduces the whole
+ * contribution is lost: run it again and fold again.  That result is the
+ * total's own table in the accumulator's buffers: its rows in the total's
+ * order, sorted or ranked as the result was when the total was saved (a merged
+ * total is neither), and folded.  Every call over the result works on it; the
+ * ones that write a new table (filter, join, rank, sort, re-key) move it out of
+ * the accumulator's buffers, mox_accumulate_reset before that takes it away.  A merge reduces the whole
  * total again, so it costs time in the total's distinct words, not the run's.
  * Completes pending asynchronous passes first.  An engine group folds member
  * 0's gathered result, on member 0.
@@ -328,7 +338,10 @@ int mox_accumulate(mox_engine* e);
  * MOX_EUTF8 reports the byte offset in the file. */
 int mox_accumulate_file(mox_engine* e, const char* path, uint64_t chunk_bytes);
 /* Drop the accumulator and free its device memory.  The last run's result, if
- * there is one, can be folded again afterwards (into the empty accumulator). */
+ * there is one, can be folded again afterwards (into the empty accumulator).
+ * A result that still is the total's own table (after a failed mox_accumulate)
+ * goes with it: the engine then has no result, and every call over one returns
+ * MOX_ESTATE until the next run. */
 int mox_accumulate_reset(mox_engine* e);
 typedef struct mox_accum_info {
   uint64_t passes;        /* results folded since create / reset */
