@@ -2,7 +2,8 @@
 // table (counts, offs, bytes): mox_bsort.hip, mox_topk.hip, mox_text.hip,
 // mox_accum.hip, mox_lookup.hip, mox_filter.hip, mox_rank.hip, mox_rekey.hip,
 // mox_find.hip, mox_join.hip, mox_hist.hip; mox_pack.h builds the pieces of the two receive-layout
-// packers on them, mox_wordhash.h the word hash and compare of the lookup and the join.
+// packers on them, mox_wordhash.h the word hash and compare of the lookup and the join,
+// mox_wordset.h the set, the build and the stream that those two share.
 // Everything is forced inline: a kernel that uses a helper compiles to what it compiled to
 // with the helper's body written out.
 //

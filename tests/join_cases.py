@@ -11,7 +11,7 @@ import top_cases
 from lookup_cases import NUL_WORDS, PREFIX_CHAIN, last_is_one_byte, near_misses, shape_table, table_words  # noqa: F401
 from top_cases import names  # noqa: F401
 
-TILE = 1024   # JN_TILE: rows per workgroup step of k_jn_build / k_jn_stream, JN_T x JN_PER
+TILE = 1024   # WS_TILE (mox_wordset.h): rows per workgroup step of k_jn_build / k_jn_stream, WS_T x WS_PER
 U64 = (1 << 64) - 1
 assert TILE == filter_cases.TILE == lookup_cases.TILE  # the compaction's and the lookup's tiles are the same rows
 

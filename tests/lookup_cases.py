@@ -7,10 +7,10 @@ import random
 
 import top_cases
 
-TILE = 1024       # LK_TILE: table words (and queries) per workgroup step, LK_T x LK_PER
-LANE_MAX = 64     # LK_LANE_MAX: a longer word is hashed and compared by a whole wave
-IDX_BITS = 21     # LK_IDX_BITS: a slot's query index + 1 ...
-TAG_BITS = 43     # LK_TAG_BITS: ... below the hash's upper bits
+TILE = 1024       # WS_TILE (mox_wordset.h): table words (and queries) per workgroup step, WS_T x WS_PER
+LANE_MAX = 64     # WS_LANE_MAX: a longer word is hashed and compared by a whole wave
+IDX_BITS = 21     # LkWords::IDX_BITS: a slot's query index + 1 ...
+TAG_BITS = 43     # LkWords::TAG_BITS: ... below the hash's upper bits
 LOOKUP_MAX = 1 << 20
 NONE = (1 << 64) - 1
 

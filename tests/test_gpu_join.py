@@ -477,6 +477,52 @@ def test_forced_collisions():
     assert hc[2] > 0 and plain[2] == 0  # every exact compare behind an equal tag ran
 
 
+# ---- 10b. the lookup and the join are two policies over one word set (mox_wordset.h)
+def cross_tables():
+    """R of 1,025 rows and T of 2,049 (a tile and one row; two tiles and one row).  They share 512 short
+    words, 6 of each side's 12 words over 64 bytes, a word T counts 0 times and b"ab" of R's b"ab" / b"ab\\0"."""
+    short = [b"w%d" % i + b"x" * (i % 20) for i in range(1006 + 1519)]
+    r_long = [b"L%d-" % i + bytes(97 + (i * j) % 26 for j in range(70 + i)) for i in range(12)]
+    t_long = r_long[::2] + [b"M%d-" % i + b"z" * (65 + 3 * i) for i in range(6)]
+    r_words = short[:1006] + r_long + [b"ab", b"ab\x00"] + [b"zero", b"a", b"r-only", b"q" * 64, b"q" * 63]
+    t_words = short[494:1006] + short[1006:] + t_long + [b"ab"] + [b"zero", b"a", b"t-only", b"q" * 64, b"Q" * 63]
+    t_counts = [0 if w == b"zero" else 3 + 2 * i for i, w in enumerate(t_words)]
+    assert len(r_words) == len(set(r_words)) == 1025 and len(t_words) == len(set(t_words)) == 2049
+    assert len(set(r_words) & set(t_words)) == 512 + 6 + 4 and len(set(r_long) & set(t_long)) == 6
+    return (r_words, list(range(1, 1026))), (t_words, t_counts)
+
+
+@pytest.mark.parametrize("path", [mox.LIB_PATH, mox.HC_LIB_PATH], ids=["plain", "hc"])
+def test_lookup_and_join_agree_on_one_pair_of_tables(path):
+    """With T as the result, the lookup of R's words finds exactly the rows that the SEMI join of R against T
+    keeps, with the kept row's count and the row's position in T.  Each library truncates the tag differently."""
+    from mox import spill
+
+    r, t = cross_tables()
+    data, offs, _ = spill.pack_pairs(r[0], [])
+    e = mox.Engine(device=0, lib_path=path)
+    try:
+        load(e, t)
+        t_items, _ = fetched(e)
+        counts, index = e.lookup_packed(data, offs, with_index=True)
+        e.accumulate()
+        load(e, r)
+        info = e.join_total("semi", "total")
+        kept, _ = fetched(e)
+    finally:
+        e.close()
+    assert len(t_items) == 2049 and info["words_in"] == 1025 and info["words_matched"] == len(kept) == 522
+    kept_count = dict(kept)
+    assert len(kept_count) == len(kept)
+    for w, c, i in zip(r[0], counts.tolist(), index.tolist()):
+        assert (i != mox.LOOKUP_NONE) == (w in kept_count), w  # found exactly where the join keeps the row
+        if w in kept_count:
+            assert c == kept_count[w] and t_items[i] == (w, c), w  # the kept row's count; the row's position in T
+        else:
+            assert c == 0, w
+    assert kept_count[b"zero"] == 0 and b"ab" in kept_count and b"ab\x00" not in kept_count
+
+
 # ---- 11. an engine group
 def test_engine_group_joins_on_member_0():
     a = b"the cat and the dog and the bird " * 3 + b"alpha a_word_of_more_than_16_bytes"

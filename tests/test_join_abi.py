@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 import join_cases as C
+import lookup_cases as LC
 import mox
 from conftest import ROOT
 from srcpins import _read, code_only, op_objects, struct_fields
@@ -124,17 +125,18 @@ def test_sum_joins():
 
 def test_constants_match_the_source():
     src = _read("map-oxidize_amd", "csrc", "mox_join.hip")
-    t = int(re.search(r"^constexpr int JN_T = (\d+);", src, re.M).group(1))
-    per = int(re.search(r"^constexpr int JN_PER = (\d+);", src, re.M).group(1))
-    assert re.search(r"^constexpr uint32_t JN_TILE = JN_T \* JN_PER;", src, re.M)
-    assert t * per == C.TILE and t % 64 == 0
-    assert 'static_assert(JN_TILE == %d, "tests/join_cases.py TILE");' % C.TILE in src
+    ws = _read("map-oxidize_amd", "csrc", "mox_wordset.h")  # the geometry is the word set's, shared with the lookup
+    t = int(re.search(r"^constexpr int WS_T = (\d+);", ws, re.M).group(1))
+    per = int(re.search(r"^constexpr int WS_PER = (\d+);", ws, re.M).group(1))
+    assert re.search(r"^constexpr uint32_t WS_TILE = WS_T \* WS_PER;", ws, re.M)
+    assert t * per == C.TILE == LC.TILE and t % 64 == 0
+    assert 'static_assert(WS_TILE == %d, "tests/lookup_cases.py and tests/join_cases.py TILE");' % C.TILE in ws
     for k in ("k_jn_build", "k_jn_stream", "k_jn_apply"):
         assert re.search(r'extern "C" __global__ .* void %s\(' % k, src) and 'q.step("%s")' % k in src, k
         assert re.search(r"^//   %s .*no scratch.*\(\d waves / SIMD\)$" % k, src, re.M), k  # its resource usage is written down
-    # the hash and the compare are the lookup's, from one header; the compaction is the filter's own
-    assert '#include "mox_wordhash.h"' in src and '#include "mox_wordhash.h"' in _read("map-oxidize_amd", "csrc", "mox_lookup.hip")
-    assert "lk_hash" in _read("map-oxidize_amd", "csrc", "mox_wordhash.h")
+    # the set, the hash and the compare are the lookup's, from one header; the compaction is the filter's own
+    assert '#include "mox_wordset.h"' in src and '#include "mox_wordset.h"' in _read("map-oxidize_amd", "csrc", "mox_lookup.hip")
+    assert '#include "mox_wordhash.h"' in ws and "lk_hash" in _read("map-oxidize_amd", "csrc", "mox_wordhash.h")
     flt = _read("map-oxidize_amd", "csrc", "mox_filter.hip")
     assert 'extern "C" int mox_join_total(' in flt and "k_fl_" not in re.sub(r"//.*", "", src)  # no second compaction
     for name in ("mox_dev.h", "mox_host.h"):
@@ -142,9 +144,26 @@ def test_constants_match_the_source():
     assert "DevBuf j_tmp;" in _read("map-oxidize_amd", "csrc", "mox_host.h")  # (freed: test_result_buffers.py)
 
 
+def test_the_word_set_is_in_one_place():
+    """The lookup and the join hold a policy, their third kernel and the host side: the compare-and-swap
+    and every probe loop over the slots are mox_wordset.h's."""
+    probe = (r"\batomicCAS\b", r"\bp = 0\b", r"\bslots\[", r"\bslots \+", r"& S\.mask", r"\bs_big\b", r"\blk_hash\b", r"\blk_equal\b")
+    ws = re.sub(r"//.*", "", _read("map-oxidize_amd", "csrc", "mox_wordset.h"))
+    for pat in probe:
+        assert re.search(pat, ws), pat
+    assert len(re.findall(r"\batomicCAS\b", ws)) == 1  # one claim
+    for name, policy in (("mox_lookup.hip", "LkWords"), ("mox_join.hip", "JnWords")):
+        code = re.sub(r"//.*", "", _read("map-oxidize_amd", "csrc", name))
+        for pat in probe:
+            assert not re.search(pat, code), (name, pat)
+        assert code.count("ws_build<%s>(S);" % policy) == 1 and code.count("ws_stream<%s>(T, S);" % policy) == 1, name
+        assert "ws_slots(" in code, name  # the one slot rule
+
+
 def test_makefile_links_the_join():
     op_objects("join", hc=True)  # mox_join_hc.o (KERNEL_FLAGS and HC_FLAGS) in libmox_hc.so, mox_join.o in the two others
-    assert "mox_wordhash.h" in re.search(r"^HOST_DEPS := (.*)$", _read("Makefile"), re.M).group(1)
+    deps = re.search(r"^HOST_DEPS := (.*)$", _read("Makefile"), re.M).group(1)
+    assert "mox_wordhash.h" in deps and "mox_wordset.h" in deps
 
 
 def test_expected_on_hand_written_cases():

@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+import join_cases as J
 import lookup_cases as C
 import mox
 from mox import dist as mdist
@@ -65,15 +66,20 @@ def test_python_surface():
 
 def test_constants_match_the_source():
     src = _read("map-oxidize_amd", "csrc", "mox_lookup.hip")
-    t = int(re.search(r"^constexpr int LK_T = (\d+);", src, re.M).group(1))
-    per = int(re.search(r"^constexpr int LK_PER = (\d+);", src, re.M).group(1))
-    assert re.search(r"^constexpr uint32_t LK_TILE = LK_T \* LK_PER;", src, re.M)
-    assert t * per == C.TILE and t % 64 == 0
-    assert int(re.search(r"^constexpr uint32_t LK_LANE_MAX = (\d+);", src, re.M).group(1)) == C.LANE_MAX
-    assert int(re.search(r"^constexpr int LK_IDX_BITS = (\d+);", src, re.M).group(1)) == C.IDX_BITS
-    assert int(re.search(r"^constexpr int LK_TAG_BITS = (\d+);", src, re.M).group(1)) == C.TAG_BITS
+    ws = _read("map-oxidize_amd", "csrc", "mox_wordset.h")  # the geometry is the word set's, shared with the join
+    t = int(re.search(r"^constexpr int WS_T = (\d+);", ws, re.M).group(1))
+    per = int(re.search(r"^constexpr int WS_PER = (\d+);", ws, re.M).group(1))
+    assert re.search(r"^constexpr uint32_t WS_TILE = WS_T \* WS_PER;", ws, re.M)
+    assert t * per == C.TILE == J.TILE and t % 64 == 0
+    assert int(re.search(r"^constexpr uint32_t WS_LANE_MAX = (\d+);", ws, re.M).group(1)) == C.LANE_MAX
+    policy = re.search(r"^struct LkWords \{(.*?)^\};", src, re.M | re.S).group(1)  # the slot split is the lookup's policy
+    assert int(re.search(r"^  static constexpr int IDX_BITS = (\d+);", policy, re.M).group(1)) == C.IDX_BITS
+    assert int(re.search(r"^  static constexpr int TAG_BITS = (\d+);", policy, re.M).group(1)) == C.TAG_BITS
     assert C.IDX_BITS + C.TAG_BITS == 64 and C.LOOKUP_MAX + 1 < 1 << C.IDX_BITS  # index + 1 fits its field
-    assert "fnv_finish" in src  # the forced-collision build truncates the hash
+    assert '#include "mox_wordset.h"' in src and '#include "mox_wordhash.h"' in ws
+    assert "fnv_finish" in _read("map-oxidize_amd", "csrc", "mox_wordhash.h")  # the forced-collision build truncates the hash
+    for k in ("k_lk_build", "k_lk_stream"):
+        assert re.search(r'^extern "C" __global__ __launch_bounds__\(WS_T\) void %s\(.*\) \{ ws_\w+<LkWords>\(.*\); \}$' % k, src, re.M), k
     op_objects("lookup", hc=True)  # mox_lookup_hc.o (KERNEL_FLAGS and HC_FLAGS) in libmox_hc.so, mox_lookup.o in the two others
 
 
