@@ -12,7 +12,7 @@ OUT := $(PKG)/mox
 
 all: $(OUT)/libmox.so $(OUT)/libmox_corpus.so $(OUT)/meduce-gpu $(OUT)/libmox_check.so $(OUT)/libmox_hc.so oracle
 
-HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_carve.h $(CSRC)/mox_dev.h $(CSRC)/mox_pack.h $(CSRC)/mox_wordhash.h $(CSRC)/mox_wordset.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
+HOST_DEPS := $(CSRC)/mox_host.h $(CSRC)/mox_carve.h $(CSRC)/mox_dev.h $(CSRC)/mox_pack.h $(CSRC)/mox_tiles.h $(CSRC)/mox_wordhash.h $(CSRC)/mox_wordset.h $(CSRC)/mox_internal.h $(CSRC)/mox_table.h include/mox.h
 
 # The calls over the device-resident result, one source each: mox_<op>.hip.
 OPS := bsort topk text accum lookup filter rank rekey find hist join

@@ -38,8 +38,9 @@
 //
 // The classifier, a round's ranks and both forms of the long-word copy + hash
 // are mox_pack.h's (pk_short, pk_ranks, pk_long_lane, pk_long_wave), which the
-// re-keying packer (mox_rekey.hip) uses too; the count kernel's sums, the scan,
-// the LDS list of big words and the tile loop are this file's.
+// re-keying packer (mox_rekey.hip) uses too; the table view and the end of the
+// count kernel are mox_tiles.h's (TileTab, tile_sums); the sums themselves, the
+// scan, the LDS list of big words and the tile loop are this file's.
 //
 // Key loads (mox_pack.h has the detail): the 16 key bytes of a row at byte
 // offset o come from three aligned 8-byte loads at o & ~7 and a funnel shift,
@@ -72,13 +73,6 @@ constexpr uint32_t AC_TILE = AC_T * AC_PER;  // rows per tile (tests/accum_cases
 constexpr uint32_t AC_COOP = 256;          // a longer long word is copied by a whole wave
 static_assert(AC_TILE == 1024, "tests/accum_cases.py TILE");
 
-// A table in generic form; nt = its tiles.
-struct AcTab {
-  const uint64_t* counts;
-  const uint64_t* offs;
-  const uint8_t* bytes;
-  uint64_t n, nt;
-};
 // Where the records go: source s's WRecs from shorts[sbase[s]], its headers at
 // blob + bbase[s], its word bytes behind its nlong[s] headers.
 struct AcOut {
@@ -91,13 +85,12 @@ struct AcOut {
 
 // tc[0 * nt + tile] = short rows, tc[1 * nt + tile] = long rows, tc[2 * nt +
 // tile] = padded long bytes of the tile; nt = a.nt + b.nt.
-extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(AcTab a, AcTab b, uint64_t* tc) {
-  __shared__ uint64_t s_w[AC_WAVES][3];
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(TileTab a, TileTab b, uint64_t* tc) {
+  const uint32_t t = threadIdx.x;
   const uint64_t nt = a.nt + b.nt;
   for (uint64_t tile = blockIdx.x; tile < nt; tile += gridDim.x) {
     const bool first = tile < a.nt;
-    const AcTab& s = first ? a : b;
+    const TileTab& s = first ? a : b;
     const uint64_t base = (first ? tile : tile - a.nt) * AC_TILE;
     uint64_t ns = 0, nl = 0, lb = 0;
 #pragma unroll
@@ -114,21 +107,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_count(AcTab a, AcTab b, 
         }
       }
     }
-    ns = wave_sum(ns);
-    nl = wave_sum(nl);
-    lb = wave_sum(lb);
-    if (lane == 0) {
-      s_w[wv][0] = ns;
-      s_w[wv][1] = nl;
-      s_w[wv][2] = lb;
-    }
-    __syncthreads();
-    if (t < 3) {
-      uint64_t v = 0;
-      for (int k = 0; k < AC_WAVES; k++) v += s_w[k][t];
-      tc[(uint64_t)t * nt + tile] = v;
-    }
-    __syncthreads();
+    tile_sums<3, AC_WAVES>({ns, nl, lb}, tc, nt, tile);
   }
 }
 
@@ -147,7 +126,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_ac_scan(uint64_t* tc, uint6
 // Every row of both tables at its scanned position (tc: k_ac_scan's output).
 // tc[3 nt + 6] is set when a short row has count 0 (such records need the
 // reduce pass's k_reduce_z; mox_kernels.hip).
-extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, uint64_t* __restrict__ tc, AcOut out) {
+extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(TileTab a, TileTab b, uint64_t* __restrict__ tc, AcOut out) {
   __shared__ uint64_t s_big_b[AC_TILE];   // long words over AC_COOP bytes: byte offset in the source's blob area,
   __shared__ uint16_t s_big_k[AC_TILE];   // ... row inside the tile
   __shared__ uint16_t s_big_r[AC_TILE];   // ... and header rank inside the tile
@@ -156,7 +135,7 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
   const uint64_t nt = a.nt + b.nt;
   for (uint64_t tile = blockIdx.x; tile < nt; tile += gridDim.x) {
     const bool first = tile < a.nt;
-    const AcTab& s = first ? a : b;
+    const TileTab& s = first ? a : b;
     const int si = first ? 0 : 1;
     const uint64_t base = (first ? tile : tile - a.nt) * AC_TILE;
     mox::WRec* S = out.shorts + out.sbase[si] + tc[tile];
@@ -205,10 +184,6 @@ extern "C" __global__ __launch_bounds__(AC_T) void k_ac_pack(AcTab a, AcTab b, u
 
 namespace {
 
-AcTab ac_tab(const uint64_t* counts, const uint64_t* offs, const uint8_t* bytes, uint64_t n) {
-  return AcTab{counts, offs, bytes, n, (n + AC_TILE - 1) / AC_TILE};
-}
-
 // The engine's result becomes the saved total (after a failed fold, and where
 // nothing else is left of the result).
 void acc_as_result(mox_engine* e) {
@@ -252,8 +227,8 @@ void acc_commit(mox_engine* e, uint64_t passes) {
 int acc_merge(mox_engine* e, DevBuf* fresh, bool* use_fresh) {
   const auto t0 = std::chrono::steady_clock::now();
   const mox_engine::Res& r = e->res;
-  const AcTab ta = ac_tab((const uint64_t*)e->a_tab[0].p, (const uint64_t*)e->a_tab[1].p, (const uint8_t*)e->a_tab[2].p, e->acc.n);
-  const AcTab tb = ac_tab(r.counts, r.offs, r.bytes, r.n);
+  const TileTab ta = tile_tab((const uint64_t*)e->a_tab[0].p, (const uint64_t*)e->a_tab[1].p, (const uint8_t*)e->a_tab[2].p, e->acc.n, AC_TILE);
+  const TileTab tb = tile_tab(r, AC_TILE);
   const uint64_t nt = ta.nt + tb.nt;
   hipStream_t s = e->stream;
   const Seq q = seq_of(e);

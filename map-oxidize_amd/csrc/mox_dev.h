@@ -1,8 +1,9 @@
 // Device-side helpers shared by the kernels over the device-resident result
 // table (counts, offs, bytes): mox_bsort.hip, mox_topk.hip, mox_text.hip,
 // mox_accum.hip, mox_lookup.hip, mox_filter.hip, mox_rank.hip, mox_rekey.hip,
-// mox_find.hip, mox_join.hip, mox_hist.hip; mox_pack.h builds the pieces of the two receive-layout
-// packers on them, mox_wordhash.h the word hash and compare of the lookup and the join,
+// mox_find.hip, mox_join.hip, mox_hist.hip; mox_tiles.h builds on them the tile passes that filter,
+// re-key, accumulate, rank and histogram share (the table view, tile sums, the scan of the tile
+// arrays), mox_pack.h the pieces of the two receive-layout packers, mox_wordhash.h the word hash and compare of the lookup and the join,
 // mox_wordset.h the set, the build and the stream that those two share.
 // Everything is forced inline: a kernel that uses a helper compiles to what it compiled to
 // with the helper's body written out.

@@ -26,7 +26,7 @@
 //     read word bytes again to decide.  Per tile: kept rows, kept bytes, kept
 //     count sum.
 //  3. k_fl_scan (one workgroup): exclusive scans of the three tile arrays, the
-//     totals behind them.  One 32-byte copy to the host
+//     totals behind them (mox_tiles.h: scan_tiles).  One 32-byte copy to the host
 //     sizes the output; MOX_FILTER_COUNT_ONLY ends here.
 //  4. k_fl_emit: a kept row's output index is its tile's scanned base, plus
 //     the wave totals before it (LDS), plus its ballot rank; its byte offset
@@ -53,18 +53,18 @@
 //
 // The device join (mox_join_total, at the end of this file) runs the same
 // count, scan and emit passes: its match bitmap (mox_join.hip) is the list
-// bitmap, and FlTab::counts may point at substituted counts.
+// bitmap, and TileTab::counts may point at substituted counts.
 //
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   k_fl_mark   12 VGPRs, 26 SGPRs,     4 B LDS, no scratch, no spills (8 waves / SIMD)
 //   k_fl_count  43 VGPRs, 90 SGPRs,    96 B LDS, no scratch, no spills (8 waves / SIMD)
-//   k_fl_scan  124 VGPRs, 72 SGPRs,   384 B LDS, no scratch, no spills (one workgroup)
+//   k_fl_scan   52 VGPRs, 72 SGPRs,   384 B LDS, no scratch, no spills (one workgroup)
 //   k_fl_emit   98 VGPRs, 74 SGPRs, 10312 B LDS, no scratch, no spills (4 waves / SIMD)
 #include <algorithm>
 #include <cstdlib>
 
-#include "mox_dev.h"
 #include "mox_host.h"
+#include "mox_tiles.h"
 
 namespace {
 
@@ -77,16 +77,10 @@ constexpr uint32_t FL_LANE_MAX = 64;         // a longer word is copied by a who
 constexpr int FL_SCAN_PER = 4;               // k_fl_scan: consecutive tiles per thread ...
 constexpr uint32_t FL_SCAN_STEP = 1024 * FL_SCAN_PER;  // ... and tiles per step of its one workgroup
 static_assert(FL_TILE == 1024, "tests/filter_cases.py TILE");
+static_assert(FL_SCAN_STEP == 4096, "tests/test_gpu_big_table.py FILTER_SCAN_STEP");
 static_assert(FL_TILE <= 65536, "s_big_k holds 16-bit rows");
 static_assert(MOX_FILTER_PREFIX_MAX == 16, "the prefix is two 8-byte words");
 
-// The result in generic form (mox_engine::Res); nt = its tiles.
-struct FlTab {
-  const uint64_t* counts;
-  const uint64_t* offs;
-  const uint8_t* bytes;
-  uint64_t n, nt;
-};
 // The predicate as the kernels take it: bounds with "no upper bound" resolved,
 // the prefix as two masked 8-byte words, the list as a bitmap over table rows.
 struct FlPred {
@@ -129,7 +123,7 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_mark(const uint64_t* idx
 // keep[tile * FL_STEPS + step] = the ballot of "row is kept" over rows
 // tile * FL_TILE + step * 64 + lane; tc[0 * nt + tile] = kept rows, tc[1 * nt +
 // tile] = kept bytes, tc[2 * nt + tile] = kept count sum of the tile.
-extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(FlTab T, FlPred P, uint64_t* __restrict__ keep, uint64_t* __restrict__ tc) {
+extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(TileTab T, FlPred P, uint64_t* __restrict__ keep, uint64_t* __restrict__ tc) {
   __shared__ uint64_t s_w[FL_WAVES][3];
   const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
   for (uint64_t tile = blockIdx.x; tile < T.nt; tile += gridDim.x) {
@@ -184,62 +178,15 @@ extern "C" __global__ __launch_bounds__(FL_T) void k_fl_count(FlTab T, FlPred P,
 }
 
 // Exclusive scans in place of the three tile arrays; the totals at tc[3 nt +
-// k], k = kept rows, kept bytes, kept count sum.  One workgroup with a running
-// carry (mox_dev.h: scan_one_wg, widened); a step takes FL_SCAN_STEP tiles of all three
-// arrays, FL_SCAN_PER consecutive ones per thread, behind one pair of barriers
-// (one array after the other, 1,024 tiles per step, took 440 us for the 89,159
-// tiles of a 91 M-word table: 264 dependent steps).
+// k], k = kept rows, kept bytes, kept count sum.  One workgroup (mox_tiles.h:
+// scan_tiles), FL_SCAN_STEP tiles of all three arrays per step.
 extern "C" __global__ __launch_bounds__(1024) void k_fl_scan(uint64_t* tc, uint64_t nt) {
-  __shared__ uint64_t ws[3][16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint64_t carry0 = 0, carry1 = 0, carry2 = 0;
-  for (uint64_t c = 0; c < nt; c += FL_SCAN_STEP) {
-    const uint64_t i0 = c + (uint64_t)FL_SCAN_PER * threadIdx.x;
-    uint64_t sum[3], inc[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      uint64_t s = 0;
-#pragma unroll
-      for (int j = 0; j < FL_SCAN_PER; j++)
-        if (i0 + j < nt) s += tc[(uint64_t)k * nt + i0 + j];
-      sum[k] = s;
-      inc[k] = wave_incscan<uint64_t>(s);
-      if (lane == 63) ws[k][wv] = inc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      uint64_t pre = 0, tot = 0;
-      for (int j = 0; j < 16; j++) {
-        if (j < wv) pre += ws[k][j];
-        tot += ws[k][j];
-      }
-      // the thread's run again (its own values, not yet overwritten), now as running sums
-      uint64_t run = (k == 0 ? carry0 : k == 1 ? carry1 : carry2) + pre + inc[k] - sum[k];
-#pragma unroll
-      for (int j = 0; j < FL_SCAN_PER; j++)
-        if (i0 + j < nt) {
-          uint64_t* a = tc + (uint64_t)k * nt + i0 + j;
-          const uint64_t v = *a;
-          *a = run;
-          run += v;
-        }
-      if (k == 0) carry0 += tot;
-      else if (k == 1) carry1 += tot;
-      else carry2 += tot;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    tc[3 * nt + 0] = carry0;
-    tc[3 * nt + 1] = carry1;
-    tc[3 * nt + 2] = carry2;
-  }
+  scan_tiles<3, FL_SCAN_PER, 1024>(tc, nt, tc + 3 * nt);
 }
 
 // Every kept row at its scanned position (keep: k_fl_count's masks, tc:
 // k_fl_scan's output).
-extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(FlTab T, const uint64_t* __restrict__ keep, const uint64_t* __restrict__ tc,
+extern "C" __global__ __launch_bounds__(FL_T) void k_fl_emit(TileTab T, const uint64_t* __restrict__ keep, const uint64_t* __restrict__ tc,
                                                              FlOut out) {
   __shared__ uint64_t s_w[FL_WAVES][2];   // a round's kept rows and kept bytes per wave
   __shared__ uint64_t s_big_b[FL_TILE];   // words over FL_LANE_MAX bytes: byte offset in the output,
@@ -317,7 +264,7 @@ struct FlTmp {
 };
 
 // f_tmp grown and laid out for the table T, the totals and (with bitmap) the list bitmap zeroed.
-int fl_scratch(mox_engine* e, const FlTab& T, bool bitmap, FlTmp* s) {
+int fl_scratch(mox_engine* e, const TileTab& T, bool bitmap, FlTmp* s) {
   const size_t bm_b = bitmap ? ((T.n + 63) / 64) * 8 + 8 : 0;
   if (int rc = carve_dev(e->f_tmp, [&](Carve& c) {
         s->tc = c.take<uint64_t>(3 * T.nt + 8);
@@ -334,7 +281,7 @@ int fl_scratch(mox_engine* e, const FlTab& T, bool bitmap, FlTmp* s) {
 
 // The count pass and the scan over a table with rows; tot[0, 4) = kept rows,
 // kept bytes, kept count sum, list words found.  Synchronises.
-int fl_select(mox_engine* e, const FlTab& T, const FlPred& P, const FlTmp& s, uint32_t grid, uint64_t* tot) {
+int fl_select(mox_engine* e, const TileTab& T, const FlPred& P, const FlTmp& s, uint32_t grid, uint64_t* tot) {
   hipStream_t st = e->stream;
   const Seq q = seq_of(e);
   hipLaunchKernelGGL(k_fl_count, dim3(grid), dim3(FL_T), 0, st, T, P, s.keep, s.tc);
@@ -349,7 +296,7 @@ int fl_select(mox_engine* e, const FlTab& T, const FlPred& P, const FlTmp& s, ui
 
 // The kept rows of T (tot: fl_select's) into the set of f_tab the result r does
 // not live in: *dst.  Synchronises; e->res is the caller's to repoint.
-int fl_emit(mox_engine* e, const mox_engine::Res& r, const FlTab& T, const FlTmp& s, uint32_t grid, const uint64_t* tot, DevBuf** dst_out) {
+int fl_emit(mox_engine* e, const mox_engine::Res& r, const TileTab& T, const FlTmp& s, uint32_t grid, const uint64_t* tot, DevBuf** dst_out) {
   hipStream_t st = e->stream;
   const Seq q = seq_of(e);
   DevBuf* dst = table_other_set(e->f_tab, r);
@@ -421,7 +368,7 @@ extern "C" int mox_filter_result(mox_engine* e, const mox_filter* f, mox_filter_
   }
   P.list_mode = f->words_mode == MOX_FILTER_WORDS_KEEP ? 2u : nq ? 1u : 0u;
 
-  const FlTab T{r.counts, r.offs, r.bytes, r.n, (r.n + FL_TILE - 1) / FL_TILE};
+  const TileTab T = tile_tab(r, FL_TILE);
   FlTmp s;
   if ((rc = fl_scratch(e, T, P.list_mode != 0, &s))) return rc;
   P.listed = s.listed;
@@ -486,7 +433,7 @@ extern "C" int mox_join_total(mox_engine* e, const mox_join* j, mox_join_info* i
   const uint64_t tn = e->acc.have ? e->acc.n : 0;  // an empty accumulator is an empty total
   const uint64_t cap = grid_cap(e, "MOX_JOIN_GRID");
   int rc;
-  FlTab T{r.counts, r.offs, r.bytes, r.n, (r.n + FL_TILE - 1) / FL_TILE};
+  TileTab T = tile_tab(r, FL_TILE);
   FlTmp s;
   if ((rc = fl_scratch(e, T, true, &s))) return rc;
   // the match bitmap is the filter's list bitmap; with an empty side it stays zero and no kernel reads the total

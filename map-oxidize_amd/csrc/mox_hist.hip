@@ -28,7 +28,7 @@
 //     arrays' exclusive scans; the totals behind them are the bins G and the
 //     tokens, which the host reads to size the output.
 //  4. k_hg_bins: the same heads again, scanned inside the tile on top of the
-//     tile's bases; every head writes at its bin index the key, the absolute
+//     tile's bases (k_hg_count ends in mox_tiles.h's tile_sums); every head writes at its bin index the key, the absolute
 //     row (the sort is stable: the head's row is the bin's lowest), its
 //     position and the exclusive count prefix at it; (n, tokens) closes both.
 //     k_hg_diff: bin_words and bin_tokens are the differences of neighbouring
@@ -47,15 +47,15 @@
 //
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   k_hg_keys    42 VGPRs, 65 SGPRs,  6152 B LDS, no scratch, no spills (8 waves / SIMD)
-//   k_hg_count   36 VGPRs, 82 SGPRs,    64 B LDS, no scratch, no spills (8 waves / SIMD)
+//   k_hg_count   32 VGPRs, 76 SGPRs,    64 B LDS, no scratch, no spills (8 waves / SIMD)
 //   k_hg_scan    80 VGPRs, 66 SGPRs,   128 B LDS, no scratch, no spills (one workgroup)
 //   k_hg_bins    52 VGPRs, 82 SGPRs,    64 B LDS, no scratch, no spills (8 waves / SIMD)
 //   k_hg_diff    12 VGPRs, 22 SGPRs,     0 B LDS, no scratch, no spills (8 waves / SIMD)
 #include <algorithm>
 #include <cstdlib>
 
-#include "mox_dev.h"
 #include "mox_host.h"
+#include "mox_tiles.h"
 
 namespace {
 
@@ -174,10 +174,10 @@ extern "C" __global__ __launch_bounds__(HG_T) void k_hg_keys(HgTab T, uint32_t m
   }
 }
 
-// th[tile] = the heads among sorted positions [tile * HG_TILE, ...), tt[tile] = the wrapping sum of their rows' counts.
-extern "C" __global__ __launch_bounds__(HG_T) void k_hg_count(HgSorted S, uint64_t* __restrict__ th, uint64_t* __restrict__ tt) {
-  __shared__ uint64_t s_h[HG_WAVES], s_c[HG_WAVES];
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+// tc[tile] = the heads among sorted positions [tile * HG_TILE, ...), tc[stride + tile] = the wrapping sum of their
+// rows' counts (the host's th and tt: two arrays of nt + 1 in one block, stride = nt + 1).
+extern "C" __global__ __launch_bounds__(HG_T) void k_hg_count(HgSorted S, uint64_t* __restrict__ tc, uint64_t stride) {
+  const uint32_t t = threadIdx.x;
   for (uint64_t tile = blockIdx.x; tile < S.nt; tile += gridDim.x) {
     uint64_t h = 0, c = 0;
     for (uint32_t j = 0; j < (uint32_t)HG_ROUNDS; j++) {
@@ -188,23 +188,7 @@ extern "C" __global__ __launch_bounds__(HG_T) void k_hg_count(HgSorted S, uint64
         if (row < S.n) c += S.counts[row];  // (always, for a permutation)
       }
     }
-    h = wave_sum(h);
-    c = wave_sum(c);
-    if (lane == 0) {
-      s_h[wv] = h;
-      s_c[wv] = c;
-    }
-    __syncthreads();
-    if (t == 0) {
-      uint64_t vh = 0, vc = 0;
-      for (int w = 0; w < HG_WAVES; w++) {
-        vh += s_h[w];
-        vc += s_c[w];
-      }
-      th[tile] = vh;
-      tt[tile] = vc;
-    }
-    __syncthreads();
+    tile_sums<2, HG_WAVES>({h, c}, tc, stride, tile);
   }
 }
 
@@ -333,12 +317,12 @@ extern "C" int mox_hist_result(mox_engine* e, const mox_hist* h, mox_hist_table*
   const uint64_t nt = (n + HG_TILE - 1) / HG_TILE;
   const uint32_t grid = (uint32_t)std::min(nt, cap);
   const bool fail_hook = test_fail_hook("MOX_TEST_FAIL_HIST");
-  // scratch: [derived keys n] [tile heads nt + 1] [tile sums nt + 1]
+  // scratch: [derived keys n] [tile heads nt + 1 | tile sums nt + 1] (one block: k_hg_count takes its base and the stride nt + 1)
   uint64_t *d_keys, *th, *tt;
   if ((rc = carve_dev(e->hg_tmp, [&](Carve& c) {
          d_keys = c.take<uint64_t>(h->key == MOX_HIST_COUNT ? 0 : n);
-         th = c.take<uint64_t>(nt + 1);
-         tt = c.take<uint64_t>(nt + 1);
+         th = c.take<uint64_t>(2 * (nt + 1));
+         tt = th + nt + 1;
        })))
     return rc;
   if ((rc = grow_pinned(e->hg_pin, 64))) return rc;
@@ -361,7 +345,7 @@ extern "C" int mox_hist_result(mox_engine* e, const mox_hist* h, mox_hist_table*
 
   // 3. the heads and the sums per tile, the bins and the tokens
   const HgSorted S{ro.keys, ro.rows, r.counts + first, n, nt};
-  hipLaunchKernelGGL(k_hg_count, dim3(grid), dim3(HG_T), 0, st, S, th, tt);
+  hipLaunchKernelGGL(k_hg_count, dim3(grid), dim3(HG_T), 0, st, S, th, nt + 1);
   q.step("k_hg_count");
   hipLaunchKernelGGL(k_hg_scan, dim3(1), dim3(HG_TOP_T), 0, st, th, tt, nt);
   q.step("k_hg_scan");

@@ -16,8 +16,8 @@
 // masked by the length (mask_low) before the NUL test, the hash and every
 // store; nothing is written past the padded word.
 #pragma once
-#include "mox_dev.h"
 #include "mox_internal.h"
+#include "mox_tiles.h"
 
 namespace mox {
 

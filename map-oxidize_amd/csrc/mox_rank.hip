@@ -39,7 +39,8 @@
 //     workgroup): their exclusive scan, the total behind them (= the table's
 //     bytes, checked by the host).
 //  4. k_rk_emit: in rounds of 256 rows, a row's byte offset is its tile's base
-//     plus a scan of the lengths; it writes the count, the offset and the
+//     plus a scan of the lengths (k_rk_len ends in mox_tiles.h's tile_sums);
+//     it writes the count, the offset and the
 //     word's bytes; offs[n] = nb closes the table.  Words of up to RK_LANE_MAX
 //     bytes are copied by their lane; longer ones (a table word reaches 16 MiB)
 //     are listed in LDS and copied by whole waves after the round, 64
@@ -72,8 +73,8 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "mox_dev.h"
 #include "mox_host.h"
+#include "mox_tiles.h"
 
 namespace {
 
@@ -289,8 +290,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_scatter(RkPass P, const 
 
 // tb[tile] = the bytes of the words of output rows [tile * RK_TILE, ...).
 extern "C" __global__ __launch_bounds__(RK_T) void k_rk_len(RkTab T, RkOrder O, uint64_t* __restrict__ tb) {
-  __shared__ uint64_t s_w[RK_WAVES];
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint32_t t = threadIdx.x;
   for (uint64_t tile = blockIdx.x; tile < T.nt; tile += gridDim.x) {
     uint64_t nb = 0;
     for (uint32_t j = 0; j < RK_ROUNDS; j++) {
@@ -300,15 +300,7 @@ extern "C" __global__ __launch_bounds__(RK_T) void k_rk_len(RkTab T, RkOrder O, 
         if (src < T.n) nb += T.offs[src + 1] - T.offs[src];
       }
     }
-    nb = wave_sum(nb);
-    if (lane == 0) s_w[wv] = nb;
-    __syncthreads();
-    if (t == 0) {
-      uint64_t v = 0;
-      for (int w = 0; w < RK_WAVES; w++) v += s_w[w];
-      tb[tile] = v;
-    }
-    __syncthreads();
+    tile_sums<1, RK_WAVES>({nb}, tb, 0, tile);
   }
 }
 

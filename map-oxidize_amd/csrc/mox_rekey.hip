@@ -53,7 +53,8 @@
 // bytes of the word.
 //
 // What the two packers have in common is in mox_pack.h, forced inline: the
-// short-row classifier (pk_short), a round's ranks (pk_ranks) and the copy +
+// short-row classifier (pk_short), a round's ranks (pk_ranks; the table view
+// and the scan are mox_tiles.h's TileTab and scan_tiles) and the copy +
 // hash of a long word by one lane and by a whole wave (pk_long_lane,
 // pk_long_wave); they take a byte range, so a window is an argument and nothing
 // else.  What differs stays here and is no template over a "row window": the
@@ -66,7 +67,7 @@
 // Resource usage (hipcc of ROCm 7.2.0: HIP 7.2.26015, AMD clang 22.0.0git
 // roc-7.2.0; the Makefile's flags, -Rpass-analysis=kernel-resource-usage):
 //   k_rekey_count  56 VGPRs,  65 SGPRs,   192 B LDS, no scratch, no spills (8 waves / SIMD)
-//   k_rekey_scan  128 VGPRs,  72 SGPRs,   384 B LDS, no scratch, no spills (one workgroup)
+//   k_rekey_scan   55 VGPRs,  72 SGPRs,   768 B LDS, no scratch, no spills (one workgroup)
 //   k_rekey_pack   84 VGPRs, 106 SGPRs, 12392 B LDS, no scratch, no spills (5 waves / SIMD)
 #include <algorithm>
 #include <cstdlib>
@@ -84,16 +85,10 @@ constexpr uint32_t RQ_COOP = 256;            // a longer long window is copied b
 constexpr int RQ_SCAN_PER = 4;               // k_rekey_scan: consecutive tiles per thread ...
 constexpr uint32_t RQ_SCAN_STEP = 1024 * RQ_SCAN_PER;  // ... and tiles per step of its one workgroup
 static_assert(RQ_TILE == 1024, "tests/rekey_cases.py TILE");
+static_assert(RQ_SCAN_STEP == 4096, "tests/test_gpu_big_table.py REKEY_SCAN_STEP");
 static_assert(RQ_TILE <= 65536, "s_big_k and s_big_r hold 16-bit rows");
 static_assert(sizeof(mox_rekey) == 64 && sizeof(mox_rekey_info) == 112, "include/mox.h");
 
-// The result in generic form (mox_engine::Res); nt = its tiles.
-struct RqTab {
-  const uint64_t* counts;
-  const uint64_t* offs;
-  const uint8_t* bytes;
-  uint64_t n, nt;
-};
 // The spec as the kernels take it: the effective set, the cap (0: none).
 struct RqSpec {
   uint64_t set0, set1, max_chars;
@@ -132,7 +127,7 @@ __device__ __forceinline__ void rq_window(const uint8_t* bytes, uint64_t o, uint
 // tc[k * nt + tile], k = 0: short rows, 1: long rows, 2: padded long bytes, 3:
 // rows whose window is not the whole word, 4: rows dropped, 5: counts dropped
 // (summed as u64) of the tile.
-extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_count(RqTab T, RqSpec P, uint64_t* __restrict__ tc) {
+extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_count(TileTab T, RqSpec P, uint64_t* __restrict__ tc) {
   __shared__ uint64_t s_w[RQ_WAVES][6];
   const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
   for (uint64_t tile = blockIdx.x; tile < T.nt; tile += gridDim.x) {
@@ -183,86 +178,26 @@ extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_count(RqTab T, RqSpec
   }
 }
 
-// Exclusive scans in place of the first three tile arrays, plain sums of the
-// other three; the six totals at tc[6 nt + k].  One workgroup with a running
-// carry, k_fl_scan's shape (mox_filter.hip): a step takes RQ_SCAN_STEP tiles of
-// the three scanned arrays, RQ_SCAN_PER consecutive ones per thread, behind one pair of
-// barriers (one array after the other through scan_one_wg, 1,024 tiles per
-// step, took 515 us for the 89,159 tiles of a 91 M-word table).  Also clears
-// the word behind the totals, k_rekey_pack's zero-count flag.
+// Exclusive scans in place of the first three tile arrays (mox_tiles.h:
+// scan_tiles, RQ_SCAN_STEP tiles per step of the one workgroup), plain sums of
+// the other three; the six totals at tc[6 nt + k].  Also clears the word behind
+// the totals, k_rekey_pack's zero-count flag.
 extern "C" __global__ __launch_bounds__(1024) void k_rekey_scan(uint64_t* tc, uint64_t nt) {
-  __shared__ uint64_t ws[3][16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint64_t carry0 = 0, carry1 = 0, carry2 = 0;
-  for (uint64_t c = 0; c < nt; c += RQ_SCAN_STEP) {
-    const uint64_t i0 = c + (uint64_t)RQ_SCAN_PER * threadIdx.x;
-    uint64_t sum[3], inc[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      uint64_t s = 0;
-#pragma unroll
-      for (int j = 0; j < RQ_SCAN_PER; j++)
-        if (i0 + j < nt) s += tc[(uint64_t)k * nt + i0 + j];
-      sum[k] = s;
-      inc[k] = wave_incscan<uint64_t>(s);
-      if (lane == 63) ws[k][wv] = inc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      uint64_t pre = 0, tot = 0;
-      for (int j = 0; j < 16; j++) {
-        if (j < wv) pre += ws[k][j];
-        tot += ws[k][j];
-      }
-      // the thread's run again (its own values, not yet overwritten), now as running sums
-      uint64_t run = (k == 0 ? carry0 : k == 1 ? carry1 : carry2) + pre + inc[k] - sum[k];
-#pragma unroll
-      for (int j = 0; j < RQ_SCAN_PER; j++)
-        if (i0 + j < nt) {
-          uint64_t* a = tc + (uint64_t)k * nt + i0 + j;
-          const uint64_t v = *a;
-          *a = run;
-          run += v;
-        }
-      if (k == 0) carry0 += tot;
-      else if (k == 1) carry1 += tot;
-      else carry2 += tot;
-    }
-    __syncthreads();
-  }
+  scan_tiles<3, RQ_SCAN_PER, 1024>(tc, nt, tc + 6 * nt);
   uint64_t sum3 = 0, sum4 = 0, sum5 = 0;
   for (uint64_t i = threadIdx.x; i < nt; i += 1024) {  // (after the scans: their registers are free)
     sum3 += tc[3 * nt + i];
     sum4 += tc[4 * nt + i];
     sum5 += tc[5 * nt + i];
   }
-  sum3 = wave_sum(sum3);
-  sum4 = wave_sum(sum4);
-  sum5 = wave_sum(sum5);
-  if (lane == 0) {
-    ws[0][wv] = sum3;
-    ws[1][wv] = sum4;
-    ws[2][wv] = sum5;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    uint64_t v = 0;
-    for (int w = 0; w < 16; w++) v += ws[threadIdx.x][w];
-    tc[6 * nt + 3 + threadIdx.x] = v;
-  }
-  if (threadIdx.x == 0) {
-    tc[6 * nt + 0] = carry0;
-    tc[6 * nt + 1] = carry1;
-    tc[6 * nt + 2] = carry2;
-    tc[6 * nt + 6] = 0;  // k_rekey_pack's flag: a short windowed row with count 0
-  }
+  tile_sums<3, 16>({sum3, sum4, sum5}, tc + 6 * nt + 3, 1, 0);  // the three totals side by side
+  if (threadIdx.x == 0) tc[6 * nt + 6] = 0;  // k_rekey_pack's flag: a short windowed row with count 0
 }
 
 // Every kept row's record at its scanned position (tc: k_rekey_scan's output).
 // tc[6 nt + 6] is set when a short windowed row has count 0 (such records need
 // the reduce pass's k_reduce_z; mox_kernels.hip).
-extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(RqTab T, RqSpec P, uint64_t* __restrict__ tc, RqOut out) {
+extern "C" __global__ __launch_bounds__(RQ_T) void k_rekey_pack(TileTab T, RqSpec P, uint64_t* __restrict__ tc, RqOut out) {
   __shared__ uint64_t s_big_b[RQ_TILE];   // long windows over RQ_COOP bytes: byte offset in the blob's word area,
   __shared__ uint16_t s_big_k[RQ_TILE];   // ... row inside the tile
   __shared__ uint16_t s_big_r[RQ_TILE];   // ... and header rank inside the tile
@@ -338,7 +273,7 @@ extern "C" int mox_rekey_result(mox_engine* e, const mox_rekey* k, mox_rekey_inf
     P.set0 |= MOX_REKEY_PUNCT_LO;
     P.set1 |= MOX_REKEY_PUNCT_HI;
   }
-  const RqTab T{r.counts, r.offs, r.bytes, r.n, (r.n + RQ_TILE - 1) / RQ_TILE};
+  const TileTab T = tile_tab(r, RQ_TILE);
   const uint64_t nt = T.nt;
   if ((rc = grow_dev(e->q_tc, (6 * nt + 8) * 8))) return rc;
   uint64_t* tc = (uint64_t*)e->q_tc.p;

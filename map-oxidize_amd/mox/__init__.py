@@ -449,6 +449,28 @@ def _check(rc, L=None):
         raise MoxError(rc, msg)
 
 
+def _info_dict(info):
+    """An info struct as a dict: its fields but ``reserved``, ms as a float."""
+    return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+
+
+def _packed(data, offs, what):
+    """A packed list of ``what`` ("words", "keys") as (uint8 array, uint64 offsets,
+    n): item i is data[offs[i]:offs[i+1]], data bytes or a numpy uint8 array
+    (None is no bytes object: TypeError, as np.frombuffer raises it)."""
+    import numpy as np
+
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = offs.size - 1
+    if n < 0:
+        raise ValueError("offs needs n + 1 entries")
+    buf = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    if n and int(offs[-1]) > buf.size:
+        raise ValueError("offsets run past the %s' bytes" % what)
+    return buf, offs, n
+
+
 class Table:
     """Owning wrapper of a mox_table (words are bytes, counts are ints)."""
 
@@ -647,7 +669,7 @@ class Engine:
         """{"passes", "words", "tokens", "device_bytes"} of the accumulator."""
         a = AccumInfo()
         self._c(self._L.mox_accumulate_info(self._h, ctypes.byref(a)))
-        return {k: int(getattr(a, k)) for k, _ in a._fields_}
+        return _info_dict(a)
 
     # -- counts of given words (mox_lookup_words)
     def lookup(self, words, with_index=False, with_info=False):
@@ -670,14 +692,7 @@ class Engine:
         (data: bytes or a numpy uint8 array, offs: uint64[n + 1])."""
         import numpy as np
 
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        n = offs.size - 1
-        if n < 0:
-            raise ValueError("offs needs n + 1 entries")
-        buf = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        if n and int(offs[-1]) > buf.size:
-            raise ValueError("offsets run past the words' bytes")
+        buf, offs, n = _packed(data, offs, "words")
         counts = np.zeros(n, dtype=np.uint64)
         index = np.full(n, LOOKUP_NONE, dtype=np.uint64) if with_index else None
         info = LookupInfo()
@@ -723,8 +738,6 @@ class Engine:
         data[offs[i]:offs[i+1]] (data: bytes or a numpy uint8 array, offs:
         uint64[n + 1]; None: no list).  ``keep``: the list is a vocabulary, not a
         stop list."""
-        import numpy as np
-
         f = Filter()
         f.min_count, f.max_count = min_count, max_count or 0  # (None, like the C struct's 0: no upper bound)
         f.min_len, f.max_len = min_len, max_len or 0
@@ -734,20 +747,13 @@ class Engine:
         f.words_mode = FILTER_WORDS_KEEP if keep else FILTER_WORDS_DROP
         f.flags = FILTER_COUNT_ONLY if count_only else 0
         if offs is not None:
-            offs = np.ascontiguousarray(offs, dtype=np.uint64)
-            n = offs.size - 1
-            if n < 0:
-                raise ValueError("offs needs n + 1 entries")
-            buf = data if isinstance(data, np.ndarray) else np.frombuffer(data or b"", dtype=np.uint8)
-            buf = np.ascontiguousarray(buf, dtype=np.uint8)
-            if n and int(offs[-1]) > buf.size:
-                raise ValueError("offsets run past the words' bytes")
+            buf, offs, n = _packed(data if data is not None else b"", offs, "words")  # (a list of empty words may come without bytes)
             f.words = buf.ctypes.data if buf.size else None
             f.word_offs = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
             f.n_words = n
         info = FilterInfo()
         self._c(self._L.mox_filter_result(self._h, ctypes.byref(f), ctypes.byref(info)))
-        return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+        return _info_dict(info)
 
     # -- the result joined against the accumulated total on the device (mox_join_total)
     def join_total(self, mode="semi", counts="result", count_only=False):
@@ -770,7 +776,7 @@ class Engine:
         j.flags = JOIN_COUNT_ONLY if count_only else 0
         info = JoinInfo()
         self._c(self._L.mox_join_total(self._h, ctypes.byref(j), ctypes.byref(info)))
-        return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+        return _info_dict(info)
 
     # -- the result ordered by count on the device (mox_rank_result), and read by rows
     def rank_result(self, ascending=False):
@@ -781,7 +787,7 @@ class Engine:
         "digit_passes", "device_bytes", "ms"}."""
         info = RankInfo()
         self._c(self._L.mox_rank_result(self._h, RANK_ASCENDING if ascending else 0, ctypes.byref(info)))
-        return {k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"}
+        return _info_dict(info)
 
     def fetch_rows(self, first, n):
         """Rows [first, first + n) of the device-resident result as a Table, in the
@@ -809,7 +815,7 @@ class Engine:
         k.flags = REKEY_TRIM_ASCII_PUNCT if punct else 0
         info = RekeyInfo()
         self._c(self._L.mox_rekey_result(self._h, ctypes.byref(k), ctypes.byref(info)))
-        return {f: (float(info.ms) if f == "ms" else int(getattr(info, f))) for f, _ in info._fields_ if f != "reserved"}
+        return _info_dict(info)
 
     # -- row ranges in the sorted result (mox_find_ranges), and the top-k of a row range (mox_top_rows)
     def find(self, keys, mode="prefix", with_sums=True, with_info=False):
@@ -835,14 +841,7 @@ class Engine:
         (data: bytes or a numpy uint8 array, offs: uint64[n + 1])."""
         import numpy as np
 
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        n = offs.size - 1
-        if n < 0:
-            raise ValueError("offs needs n + 1 entries")
-        buf = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        if n and int(offs[-1]) > buf.size:
-            raise ValueError("offsets run past the keys' bytes")
+        buf, offs, n = _packed(data, offs, "keys")
         first = np.zeros(n, dtype=np.uint64)
         last = np.zeros(n, dtype=np.uint64)
         sums = np.zeros(n, dtype=np.uint64) if with_sums else None
@@ -856,7 +855,7 @@ class Engine:
         if with_sums:
             out += (sums,)
         if with_info:
-            out += ({k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"},)
+            out += (_info_dict(info),)
         return out
 
     def top_rows(self, first, n, k=10):
@@ -905,7 +904,7 @@ class Engine:
         finally:
             self._L.mox_hist_free(t)
         if with_info:
-            out += ({k: (float(info.ms) if k == "ms" else int(getattr(info, k))) for k, _ in info._fields_ if k != "reserved"},)
+            out += (_info_dict(info),)
         return out
 
     def stats(self):
