@@ -46,12 +46,9 @@ static_assert(sizeof(BRec) == 16, "BRec is one 16-byte load");
 constexpr uint32_t WIN = 7;                      // window bytes per level
 constexpr uint32_t AUX_MORE = 8;                 // aux: the word continues past the window
 constexpr int OS_THREADS = 256;
-#ifndef MOX_OS_ITEMS
-#define MOX_OS_ITEMS 16
-#endif
-constexpr int OS_ITEMS = MOX_OS_ITEMS;           // records per thread
+constexpr int OS_ITEMS = 16;                     // records per thread
 constexpr int OS_TILE = OS_THREADS * OS_ITEMS;   // 4,096 records per tile (16 KiB stage per 1,024)
-constexpr int OS_WG_PER_CU = OS_ITEMS <= 8 ? 4 : 2;
+constexpr int OS_WG_PER_CU = 2;
 constexpr int OS_WAVES = OS_THREADS / 64;
 constexpr int OS_DIGITS = 12;                    // key bytes 0..7 (0 = aux), run bytes 0..3
 // look-back status word of (tile, digit): flag in bits 63..62, count below

@@ -89,11 +89,7 @@ int realloc_sized(mox_engine* e, const Caps& c) {
   Work n = e->w;
   // a multiple of 2 QF_MAX: every one of a region's QF_MAX slices holds an even
   // number of records, so k_map's paired records stay sector-aligned
-#ifndef MOX_COLD_PAD
-#define MOX_COLD_PAD 0  // experiment: extra 2 QF_MAX-record steps per region (region stride off a power of two)
-#endif
-  n.cold_cap = (uint32_t)std::min<uint64_t>(((c.cold_cap + 2 * QF_MAX - 1) & ~(uint64_t)(2 * QF_MAX - 1)) + MOX_COLD_PAD * 2 * QF_MAX,
-                                            COLD_CAP_MAX);
+  n.cold_cap = (uint32_t)std::min<uint64_t>((c.cold_cap + 2 * QF_MAX - 1) & ~(uint64_t)(2 * QF_MAX - 1), COLD_CAP_MAX);
   static_assert(COLD_CAP_MAX % (2 * QF_MAX) == 0 && COLD_CAP_MAX < (1u << 24), "cold_cap clamp (k_map: __umul24)");
   n.spill_cap = (uint32_t)std::min<uint64_t>(c.spill_cap, 0xFFFFFFF0u);
   n.w_cap = c.w_cap;
@@ -284,7 +280,7 @@ void launch_reduce_tail(mox_engine* e, const Corpus& c, const Seq& q, bool zero)
   hipLaunchKernelGGL(k_split_scatter, dim3(NB), dim3(1024), 0, s, w);
   q.step("k_split_scatter");
   // count-1 small units first: its hash-collision fallbacks join k_reduce's work list
-  hipLaunchKernelGGL(k_reduce_sort1, dim3(MOX_S1_WG * e->n_cu), dim3(256), 0, s, w);  // 4 waves per workgroup, one unit per wave
+  hipLaunchKernelGGL(k_reduce_sort1, dim3(S1_WG * e->n_cu), dim3(256), 0, s, w);  // 4 waves per workgroup, one unit per wave
   q.step("k_reduce_sort1");
   hipLaunchKernelGGL(k_reduce_sort2, dim3(8 * e->n_cu), dim3(64), 0, s, w);  // one wave per unit of 513..1024 records
   q.step("k_reduce_sort2");
@@ -350,9 +346,6 @@ void enqueue_pass(mox_engine* e, const Corpus& c, const Seq& q, bool side = fals
   // 1. hot dictionary from a sample
   if (sided) {
     use_dset(e, e->dcur ^ 1);
-    // after the previous pass's k_map (ev_mapped): beside its reduce tail
-    if (e->mapped_pending) (void)hipStreamWaitEvent(e->dstream, e->ev_mapped, 0);
-    e->mapped_pending = false;
     hipLaunchKernelGGL(k_dict_zero, dim3(64), dim3(256), 0, e->dstream, w);
     launch_dict(e, c, e->dstream, q);
     (void)hipEventRecord(e->ev_dready, e->dstream);
@@ -370,13 +363,6 @@ void enqueue_pass(mox_engine* e, const Corpus& c, const Seq& q, bool side = fals
   hipLaunchKernelGGL(k_map, dim3(grid), dim3(MAP_THREADS), map_lds_bytes(), s, c, w, nrows, 0u);
   q.step("k_map");
   q.rec(2);
-#ifndef MOX_SIDE_AFTER_MAP
-#define MOX_SIDE_AFTER_MAP 0  // 1: measured slower end to end (profiles/r05/c2_side_dict_overlap.txt)
-#endif
-  if (MOX_SIDE_AFTER_MAP && side && !q.timing && !q.sync_each) {  // the next async pass's side build waits for this k_map
-    (void)hipEventRecord(e->ev_mapped, s);
-    e->mapped_pending = true;
-  }
   // 3. lanes
   hipLaunchKernelGGL(k_unicode, dim3(1024), dim3(256), 0, s, c, w, e->tables);  // + dictionary totals
   q.step("k_unicode");
@@ -719,8 +705,7 @@ int engine_create_one(const mox_config* cfg, int dev, mox_engine** out) {
   }
   for (auto& ev : e->ev) (void)hipEventCreate(&ev);
   if (hipStreamCreateWithFlags(&e->dstream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_dready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_mapped, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&e->ev_dready, hipEventDisableTiming) != hipSuccess) {
     mox_engine_destroy(e);
     return fail(MOX_EHIP, "side stream / events: creation failed");
   }
@@ -1104,7 +1089,6 @@ void mox_engine_destroy(mox_engine* e) {
   if (e->stream) (void)hipStreamDestroy(e->stream);
   if (e->dstream) (void)hipStreamDestroy(e->dstream);
   if (e->ev_dready) (void)hipEventDestroy(e->ev_dready);
-  if (e->ev_mapped) (void)hipEventDestroy(e->ev_mapped);
   delete e;
 }
 

@@ -129,17 +129,11 @@ struct mox_engine {
   // dictionary buffers are double-buffered (dsets): a side build writes the set
   // the previous pass did not use, and the pass before that one has completed
   // on the host by then (mox_run_range_async completes pass k - 1 before it
-  // returns), so the side stream waits for nothing.
+  // returns), so the side stream waits for nothing.  (A side build that waited
+  // for pass k's k_map, to run beside the reduce tail only, measured 1.1 %
+  // slower end to end: profiles/r05/c2_side_dict_overlap.txt.)
   hipStream_t dstream = nullptr;
   hipEvent_t ev_dready = nullptr;
-  // MOX_SIDE_AFTER_MAP=1 (mox_engine.hip): recorded right after an async
-  // pass's k_map, and the next pass's side build waits for it, so that the
-  // build runs beside the reduce tail rather than beside k_map (where the
-  // trace shows k_sample stretching k_map's launches by 10-120 us).  Measured
-  // 1.1 % slower end to end (the tail pays more than k_map saves), so off by
-  // default (profiles/r05/c2_side_dict_overlap.txt).
-  hipEvent_t ev_mapped = nullptr;
-  bool mapped_pending = false;  // ev_mapped recorded by a pass whose successor has not waited on it yet
   struct DictSet {
     WRec* cand = nullptr;
     uint32_t* dict_hist = nullptr;

@@ -18,25 +18,15 @@ constexpr int MAP_MIN_WAVES = 1;
 #error "MOX_ABLATE is an experiment build (tools/build_variant.sh): not for the product library"
 #endif
 constexpr int MAP_LOADERS = 1;              // loader waves
-#ifndef MOX_LD_SLEEP
-#define MOX_LD_SLEEP 1  // k_map loader's poll for a free ring slot (s_sleep units of 64 clocks)
-#endif
-#ifndef MOX_CO_SLEEP
-#define MOX_CO_SLEEP 1  // k_map consumer's poll for a loaded row
-#endif
-#ifndef MOX_RING
-#define MOX_RING 32
-#endif
-constexpr int RING = MOX_RING;              // k_map row ring slots (LDS)
+constexpr int LD_SLEEP = 1;                 // k_map loader's poll for a free ring slot (s_sleep units of 64 clocks)
+constexpr int CO_SLEEP = 1;                 // k_map consumer's poll for a loaded row
+constexpr int RING = 32;                    // k_map row ring slots (LDS)
 // LDS hot dictionary: single-word slots, two choices per word (dict_s1 / dict_s2,
 // mox_kernels.hip); k_dict_pick picks up to DICT_MAX_WORDS candidates.
 // (12-byte keys with the count inside the 16-byte slot held 4,620 words
 // instead of 3,660 and cut the C2 cold records 5 %, but k_map got 15-24 us
 // slower than k_reduce gained: profiles/r06/dict12_ab.txt, not kept.)
-#ifndef MOX_DICT_SLOTS
-#define MOX_DICT_SLOTS 5120
-#endif
-constexpr int DICT_SLOTS = MOX_DICT_SLOTS;
+constexpr int DICT_SLOTS = 5120;
 constexpr int DICT_MAX_WORDS = DICT_SLOTS < 4096 ? DICT_SLOTS : 4096;
 constexpr size_t DICT_CNT_BYTES = (size_t)DICT_SLOTS * 4;  // k_map's count array
 static_assert(DICT_SLOTS % 32 == 0 && DICT_SLOTS <= 65536 && DICT_MAX_WORDS <= DICT_SLOTS, "dictionary geometry");
@@ -50,14 +40,10 @@ constexpr int TOKMAX = ROW / 2;             // token starts per row (at most eve
 constexpr int SLOT = ROW;
 constexpr int PAY = ROW - 32;               // 992 payload bytes per row
 constexpr int KSEL_N = 17 * 4;              // k_map key selectors: key length 0..16 x byte offset 0..3
-#ifndef MOX_LD_GROUPS
-#define MOX_LD_GROUPS 4  // 3: k_map +2.5-4 % on C2 (interleaved A/B)
-#endif
-#ifndef MOX_LD_GROUP
-#define MOX_LD_GROUP 6
-#endif
-constexpr int LD_GROUP = MOX_LD_GROUP;      // loader: rows per register group
-constexpr int LD_GROUPS = MOX_LD_GROUPS;    // groups in flight (LD_GROUP x (LD_GROUPS-1) rows outstanding)
+constexpr int LD_GROUP = 6;                 // loader: rows per register group
+// groups in flight (LD_GROUP x (LD_GROUPS-1) rows outstanding); with 3, k_map
+// took 2.5-4 % longer on C2 (interleaved A/B)
+constexpr int LD_GROUPS = 4;
 constexpr int MAP_CONSUMERS = MAP_WAVES - MAP_LOADERS;
 // (Rows loaded by their own wave by LDS-DMA, with no loader or ring, removed the
 // ring's supply floor but measured 1.5-4 % slower on the whole kernel; two rows
@@ -106,24 +92,16 @@ constexpr int SUB_BITS_MAX = 12;
 constexpr int SUB_N = 1 << SUB_BITS_MAX;
 constexpr int U_MAX = NB * SUB_N;           // reduce units
 constexpr int SUB_PER_T = SUB_N / 1024;     // sub-buckets per thread in the 1024-thread unit kernels
-#ifndef MOX_SPLIT_MIN
-#define MOX_SPLIT_MIN 8192
-#endif
 // records up to which a partition is never split: k_reduce takes it whole, in
 // at most 4 table sub-passes of RED_CAP distinct keys (the exchange's reduce
 // pass at C3, ~3.3 K weighted records per partition: 2048 -> 8192 took its
 // span from 556 to 517 us and the N = 2 exchange from 1.07-1.10 to
 // 0.86-0.88 ms, profiles/r06/split_min_ab_g31.txt)
-constexpr uint32_t SPLIT_MIN = MOX_SPLIT_MIN;
+constexpr uint32_t SPLIT_MIN = 8192;
 constexpr uint32_t SPLIT_TARGET = 320;      // records per sub-bucket aimed at
 constexpr uint32_t SMALL_CAP = 512;         // sub-buckets up to this many records: k_reduce_small
-#ifndef MOX_S1_WG
-#define MOX_S1_WG 4  // k_reduce_sort1 workgroups per CU (its launch bound and persistent grid; 4 -> 128 VGPRs)
-#endif
-#ifndef MOX_SPLIT_PER_REGION
-#define MOX_SPLIT_PER_REGION 4
-#endif
-constexpr uint32_t SPLIT_PER_REGION = MOX_SPLIT_PER_REGION;  // sample: the first records of every map workgroup's region
+constexpr int S1_WG = 4;                    // k_reduce_sort1 workgroups per CU (its launch bound and persistent grid; 4 -> 128 VGPRs)
+constexpr uint32_t SPLIT_PER_REGION = 4;    // sample: the first records of every map workgroup's region
 constexpr uint32_t SPLIT_SAMPLE = 256 * SPLIT_PER_REGION;      // records sampled for the distinct-fraction estimate
 constexpr int LC_BITS = 4096;               // linear-counting bitmap of the sample (4 bits per sample)
 

@@ -717,9 +717,6 @@ __device__ __forceinline__ uint32_t lds_fetch_add_lane(uint32_t* p, uint32_t v) 
 __device__ __forceinline__ void lds_add_lane(uint32_t* p, uint32_t v) {
   asm volatile("ds_add_u32 %0, %1" ::"v"(lds_addr(p)), "v"(v) : "memory");
 }
-#ifndef MOX_RED_LAZYCAP
-#define MOX_RED_LAZYCAP 1  // k_reduce: new keys counted without a returning atomic, RED_CAP tested after the stream (-0.8 %)
-#endif
 // compiler + LDS ordering between lanes of one wave (LDS executes a wave's
 // instructions in order; this keeps the compiler from reordering across it)
 __device__ __forceinline__ void wave_lds_fence() {
@@ -1263,7 +1260,7 @@ extern "C" __global__ __launch_bounds__(MAP_THREADS, MAP_MIN_WAVES) void k_map(C
         bool ok = !need || __hip_atomic_load(&sfree[t % RING], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == t - RING + 1;
         if (!__all(ok)) {  // (the loop only when a slot is still taken: see the wait above)
           do {
-            __builtin_amdgcn_s_sleep(MOX_LD_SLEEP);
+            __builtin_amdgcn_s_sleep(LD_SLEEP);
             if (!ok) ok = __hip_atomic_load(&sfree[t % RING], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == t - RING + 1;
           } while (!__all(ok));
         }
@@ -1326,7 +1323,7 @@ extern "C" __global__ __launch_bounds__(MAP_THREADS, MAP_MIN_WAVES) void k_map(C
       if (u >= n) break;
       const uint32_t slot = u % RING;
       while (__hip_atomic_load(&sready[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != u + 1)
-        __builtin_amdgcn_s_sleep(MOX_CO_SLEEP);
+        __builtin_amdgcn_s_sleep(CO_SLEEP);
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
       uint8_t* sl = ring + slot * SLOT;
       const uint64_t sbase = base0 + (rb + u) * PAY - 16;
@@ -2034,21 +2031,11 @@ extern "C" __global__ __launch_bounds__(1024) void k_scatter(Work w) {
 // more distinct keys than RED_CAP is redone in 2^k sub-passes over the next
 // hash bits.
 // RED_BK, RED_SLOTS, RED_CAP, RED_SORTB: mox_internal.h (the host sizes the LDS)
-#ifndef MOX_RED_UNROLL
-#define MOX_RED_UNROLL 1  // 64-record chunks (round-4 A/B, profiles/r04/c2_k_reduce_depth_ab.txt)
-#endif
-constexpr int RED_UNROLL = MOX_RED_UNROLL;
-#ifndef MOX_RED_DYN
-#define MOX_RED_DYN 1  // k_reduce waves take chunk pairs from an LDS ticket (0: static equal shares)
-#endif
-#ifndef MOX_RED_TAB
-#define MOX_RED_TAB 1  // k_reduce: ticket -> region table (0: binary search per ticket)
-#endif
-#ifndef MOX_RED_DEPTH
-#define MOX_RED_DEPTH 3  // k_reduce chunks per ticket: two chunks' loads in flight while one is inserted
-#endif
-constexpr uint32_t RED_TICKET = 64 * MOX_RED_UNROLL * MOX_RED_DEPTH;  // records per k_reduce ticket
-constexpr int RED_TAB_MAX = RED_SORTB;                  // ticket table entries (u16, in the fill space)
+constexpr int RED_UNROLL = 1;  // 64-record chunks (round-4 A/B, profiles/r04/c2_k_reduce_depth_ab.txt)
+// records per k_reduce ticket: the waves take tickets of three chunks from an
+// LDS counter, two chunks' loads in flight while one is inserted
+constexpr uint32_t RED_TICKET = 64 * RED_UNROLL * 3;
+constexpr int RED_TAB_MAX = RED_SORTB;                  // ticket -> region table entries (u16, in the fill space)
 
 struct RedLds {
   uint4* tag4;             // RED_BK x 4 key hashes (0 = free)
@@ -2057,7 +2044,7 @@ struct RedLds {
   uint16_t* idx;           // RED_CAP: slots in output order
   uint16_t* bin;           // RED_SORTB + 1: bin counts, then bin starts (exclusive scan)
   uint16_t* fill;          // RED_SORTB: bin fill cursors
-  uint32_t* misc;          // [0] uniques [1] overflow [2] chunk ticket (MOX_RED_DYN) [3] key bytes
+  uint32_t* misc;          // [0] uniques [1] overflow [2] chunk ticket [3] key bytes
   uint32_t* dbg;           // DBG_COUNT: [0] slow inserts [1] slow iterations [2] publication retries
   Ctl* ctl;                // path counters (MOX_PATHS builds)
   bool plain;
@@ -2202,9 +2189,6 @@ __device__ __noinline__ void red_zero_records(const RedLds& s, const WRec* wsrc,
   }
 }
 
-#ifndef MOX_RED_FASTINS
-#define MOX_RED_FASTINS 1  // red_try also inserts a new key into a free slot of its first two buckets
-#endif
 enum : int { RED_MISS = 0, RED_ADDED = 1, RED_NEW = 2 };
 // Fast path: the key's home bucket and the next one (keys overflow at most one
 // bucket at this table load), their tags read together.  A bucket's taken
@@ -2258,7 +2242,6 @@ __device__ __forceinline__ int red_try(const RedLds& s, uint32_t h, uint4 k, uin
     else atomicAdd(&s.cnt[sl], (unsigned long long)c);
     return RED_ADDED;
   }
-#if MOX_RED_FASTINS
   // claim: CAS from this slot on along the two buckets.  A slot lost to
   // another key moves the claim to the next slot (the slots before it are
   // taken by other keys and stay so); a slot lost to tag h was most often
@@ -2295,9 +2278,6 @@ __device__ __forceinline__ int red_try(const RedLds& s, uint32_t h, uint4 k, uin
       return RED_MISS;
     }
   }
-#else
-  return RED_MISS;
-#endif
 }
 
 // Table order of short words: (h32, hash32b, key).  Every reduce kernel uses
@@ -2619,9 +2599,8 @@ extern "C" __global__ __launch_bounds__(SC_THREADS) void k_unit_scan(Work w) { u
 // retries, and the BUSY holder finishes within the same loop iteration, so no
 // lane ever waits on another wave's progress.  Leftover single records are
 // written after the stream.
-#ifndef MOX_SPLIT_STAGE
-#define MOX_SPLIT_STAGE 1  // slices of QF-region partitions go out LDS-staged (0: record pairs, the round-3 scheme)
-#endif
+// Slices of QF-region partitions go out LDS-staged instead (for them, record
+// pairs were the round-3 scheme).
 // LDS-staged scatter of slice q (regions q, q + qf, ...) of partition b: the
 // slice's records in chunks of SST_CH, each chunk counting-sorted by sub-bucket
 // in LDS, then every sub-bucket's run of the chunk written with consecutive
@@ -2818,7 +2797,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_split_scatter(Work w) {
   if (w.b_recs[b] == 0) {
     // no cold records (the exchange's and mox_reduce_pairs' reduce passes):
     // only the weighted records below
-  } else if (sliced && stage_fits && MOX_SPLIT_STAGE) {
+  } else if (sliced && stage_fits) {
     SplitStage S;
     S.stage = reinterpret_cast<uint4*>(xs);
     S.sidx = reinterpret_cast<uint16_t*>(xs + SST_CH * 16);
@@ -2853,7 +2832,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_split_scatter(Work w) {
       }
   }
   __syncthreads();
-  if (sliced && MOX_SPLIT_STAGE) return;  // (no pair slots)
+  if (sliced) return;  // (no pair slots)
   // leftover singles (odd counts)
 #pragma unroll
   for (int j = 0; j < SUB_PER_T; j++) {
@@ -3387,7 +3366,7 @@ __device__ __forceinline__ void sort_reduce_unit(const Work& w, uint32_t u, cons
   wave_lds_fence();  // this unit's LDS reads before the next unit's writes
 }
 
-extern "C" __global__ __launch_bounds__(64 * S1_WAVES, MOX_S1_WG) void k_reduce_sort1(Work w) {
+extern "C" __global__ __launch_bounds__(64 * S1_WAVES, S1_WG) void k_reduce_sort1(Work w) {
   __shared__ uint4 skey[S1_WAVES][SMALL_CAP];
   __shared__ uint16_t shp[S1_WAVES][SMALL_CAP + 2];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

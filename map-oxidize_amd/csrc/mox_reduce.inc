@@ -26,8 +26,6 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
   s.ctl = w.ctl;
   if (threadIdx.x < 8) dbgc[threadIdx.x] = 0;
   const int tid = threadIdx.x, lane = tid & 63;
-  [[maybe_unused]] const int wv = tid >> 6;
-  [[maybe_unused]] constexpr int NWV = RED_THREADS / 64;
   const uint32_t G = reg_grid(w), RC = reg_cap(w);  // cold regions per partition (<= MAX_MAP_GRID), records per region
   uint32_t* tags = reinterpret_cast<uint32_t*>(s.tag4);
   // an overflowed map, directory or split means this attempt is rerun with
@@ -69,7 +67,7 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
     if (split) { wsrc = w.split_w; ws0 = ud.win_off; ws1 = ws0 + ud.win_n; }
     else { wsrc = w.w_sorted; ws0 = w.w_off[b]; ws1 = w.w_off[b + 1]; }
     const uint64_t out0 = ud.rec_off;
-    // split unit: its contiguous cold range is cut into NWV wave chunks
+    // split unit: one contiguous cold range
     const uint64_t kin0 = split ? ud.in_off : 0;
     const uint32_t kin_n = split ? ud.in_n : 0;
     const bool stamp = MOX_ABL(w.dbg, DBG_STAMP) && tid == 0 && !split;
@@ -85,14 +83,13 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
       if (tid == 0) { s.misc[0] = 0; s.misc[1] = 0; s.misc[2] = 0; s.misc[3] = 0; }
       // region prefix of a whole partition (the map workgroups' regions one after
       // another), in the sort index / bin space, which is free until the sort
-      bool tab = false;  // ticket -> region table built (MOX_RED_TAB)
+      bool tab = false;  // ticket -> region table built
       if (!split) {
         uint64_t tot;
         const uint32_t cn = tid < (int)G ? cold_n_at(w, G, tid, b) : 0u;
         const uint64_t ex = block_exscan(cn, red_wsum, tot);
         if (tid < (int)G) rpre[tid] = (uint32_t)ex;
         if (tid == 0) rpre[G] = (uint32_t)tot;
-#if MOX_RED_DYN && MOX_RED_TAB
         // region of every ticket start (record j RED_TICKET): the region holding
         // it, written by that region's thread from its own prefix and count, so
         // a wave finds a ticket's region in one LDS read instead of a binary
@@ -102,38 +99,33 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
           for (uint32_t j = (uint32_t)((ex + RED_TICKET - 1) / RED_TICKET); (uint64_t)j * RED_TICKET < ex + cn; j++)
             rtab[j] = (uint16_t)tid;
         }
-#endif
       }
       __syncthreads();
       for (int rep = 0; rep < (MOX_ABL(w.dbg, DBG_RED_TWICE) ? 2 : 1); rep++)
       // cold records: the unit's records as one flat index space (whole
       // partition: region g = map workgroup g, at rpre[g]; split unit: one
-      // contiguous range), cut into NWV equal wave shares in 64-record steps so
-      // the waves finish together and every chunk is full but the wave's last.
+      // contiguous range), handed to the waves in tickets of RED_TICKET records.
       // Each lane walks forward through the regions (its records ascend by 64
-      // per step), the next chunk's loads in flight while the current one is
+      // per step), the next chunks' loads in flight while the current one is
       // inserted.
       {
-#if MOX_RED_DYN
         if (rep) {  // DBG_RED_TWICE: the chunk tickets restart for the second stream
           __syncthreads();
           if (tid == 0) s.misc[2] = 0;
           __syncthreads();
         }
-#endif
         const uint32_t n = split ? kin_n : rpre[G];
         constexpr uint32_t CH = 64 * RED_UNROLL;
         // in_sub as one masked compare: hash bits [32 - shift0 - kk, 32 - shift0)
         // equal sub (shift0 + kk <= 32 in every pass that runs; kk == 0: all)
         const uint32_t sub_mask = kk ? ((1u << kk) - 1u) << (32 - shift0 - kk) : 0u;
         const uint32_t sub_val = kk ? sub << (32 - shift0 - kk) : 0u;
-#if MOX_RED_DYN
-        // dynamic shares: waves take the next 2 chunks from an LDS ticket, so
-        // they finish within ~2 chunks of each other (static equal shares left
+        // dynamic shares: waves take the next chunks from an LDS ticket, so
+        // they finish within a ticket of each other (static equal shares left
         // the slowest wave ~25 us behind per partition at C2,
         // profiles/r03_k_reduce_stamps.txt: insert_tail)
         constexpr uint32_t SCH = RED_TICKET;
-        static_assert(RED_TICKET == MOX_RED_DEPTH * CH, "a ticket is MOX_RED_DEPTH chunks");
+        static_assert(RED_TICKET == 3 * CH, "a ticket is three chunks");
         const uint32_t a1 = n;
         auto grab = [&]() -> uint32_t {
           uint32_t v = 0;
@@ -141,11 +133,6 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
           return __builtin_amdgcn_readfirstlane(v);
         };
         const uint32_t a0 = grab();
-#else
-        const uint32_t per = (((n + NWV - 1) / NWV) + 63) & ~63u;
-        const uint32_t a0 = (uint32_t)wv * per < n ? (uint32_t)wv * per : n;
-        const uint32_t a1 = n - a0 < per ? n : a0 + per;
-#endif
         const uint4* ubase = split ? w.split_k + kin0 : w.cold + b * RC;  // region g at + g NB RC
         const uint64_t gstride = (uint64_t)NB * RC;
         // lane state: region r holds flat records [rs, re).  (A per-lane 64-bit
@@ -232,14 +219,11 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
               nnew += (uint32_t)__popcll(__ballot(r == RED_NEW));
             }
             // the chunk's new keys counted at once (one lane, one LDS atomic);
-            // past RED_CAP the unit is redone in sub-passes
+            // past RED_CAP the unit is redone in sub-passes.  No returning
+            // atomic: -0.8 % against a per-chunk test of the returned count
+            // (profiles/r05/k_reduce_lazycap_ab.txt)
             if (nnew && lane == 0) {
-#if MOX_RED_LAZYCAP
               lds_add_lane(&s.misc[0], nnew);  // the RED_CAP test once the stream is done
-#else
-              const uint32_t u0 = lds_fetch_add_lane(&s.misc[0], nnew);
-              if (u0 + nnew > (uint32_t)RED_CAP) s.misc[1] = 1;
-#endif
             }
             RED_MARK(2);
 #pragma unroll
@@ -256,7 +240,6 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
         };
         uint32_t c = a0;
         uint4 A[RED_UNROLL], B[RED_UNROLL];
-#if MOX_RED_DYN && MOX_RED_DEPTH == 3
         // tickets of three chunks [c, c + CH), [c + CH, c + 2 CH), [c + 2 CH,
         // c + 3 CH): two chunks' loads in flight while one is inserted (the
         // stream is bound by the bytes each wave keeps in flight)
@@ -278,34 +261,6 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
           process(C, c + 2 * CH);
           c = cn;
         }
-#elif MOX_RED_DYN
-        // chunk pairs [c, c + CH), [c + CH, c + SCH) of one ticket, the next
-        // ticket's first chunk in flight while the second is inserted
-        if (c < a1) load(c, A);
-        while (c < a1) {
-          load(c + CH, B);
-          // the next ticket's LDS atomic goes out before this chunk's probes
-          uint32_t tv = 0;
-          if (lane == 0) tv = lds_fetch_add_lane(&s.misc[2], SCH);
-          process(A, c);
-          const uint32_t cn = __builtin_amdgcn_readfirstlane(tv);
-          seek(cn);
-          load(cn, A);
-          process(B, c + CH);
-          c = cn;
-        }
-#else
-        if (c < a1) load(c, A);
-        while (c < a1) {
-          load(c + CH, B);
-          process(A, c);
-          c += CH;
-          if (c >= a1) break;
-          load(c + CH, A);
-          process(B, c);
-          c += CH;
-        }
-#endif
       }
       if (stamp) w.stamps[b * 8 + 1] = __builtin_amdgcn_s_memrealtime();  // wave 0 done streaming
       // A weighted record with count 0 (mox_reduce_pairs lets one through, and a
@@ -370,13 +325,11 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
         (void)MOX_CHK(w, ok, CHK_RED_TABLE);
       }
 #endif
-#if MOX_RED_LAZYCAP
       if (s.misc[0] > (uint32_t)RED_CAP) {  // (uniform: every thread reads the settled count)
         __syncthreads();
         if (tid == 0) s.misc[1] = 1;
         __syncthreads();
       }
-#endif
       if (s.misc[1]) {  // too many distinct keys for one table: split further, redo the unit
         kk++;
         // the redo does not see this attempt's keys (readers take a slot's key
@@ -475,6 +428,8 @@ extern "C" __global__ __launch_bounds__(RED_THREADS, 8) void MOX_RED_KERNEL(Work
   }
 #ifdef MOX_RED_STATS
   if (lane == 0 && w.stamps) {
+    const int wv = tid >> 6;
+    constexpr int NWV = RED_THREADS / 64;
     unsigned long long* o = w.stamps + 8 * 4096 + 8 * 1024 * MAP_WAVES + ((uint64_t)blockIdx.x * NWV + wv) * 4;
     for (int k = 0; k < 4; k++) o[k] = rcyc[k];
   }

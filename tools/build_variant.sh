@@ -3,6 +3,9 @@
 # (bench.py / tests load it with MOX_LIB=build/var_NAME/libmox.so, or
 # mox.Engine(lib_path=...)).
 # Usage: bash tools/build_variant.sh NAME "-DFLAG ..."
+# Flags the sources know: the instrumentation builds -DMOX_ABLATE, -DMOX_STAMP,
+# -DMOX_RED_STATS, -DMOX_SR_STATS and -DMOX_ISA_MARKS.  The settled tunables are
+# plain constants now: the other arm of an A/B is another commit's sources (SRC).
 # SRC=DIR builds DIR's sources instead of map-oxidize_amd/csrc (e.g. an older
 # commit's, exported with tools/export_src.sh).
 set -e
